@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — rpca ALM iterations/sec on a 20000x512 fp64 D (BASELINE.json config 2) on N MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
-A "step" is one complete rpca solve (the reference's hot loop, /root/reference/src/robustPCA.jl:156-239, run to its own
+A "step" is one complete rpca solve (the reference's hot loop, src/robustPCA.jl:156-239, run to its own
 convergence test) on a synthetic rank-16 + 5%-sparse D that is already resident in HBM; outputs A, E stay in HBM.
-value = ALM iterations completed in the K timed steps / wall time (max over ranks).  N>1 row-shards the SAME 20000x512
-problem (strong scaling) and exchanges the N x N Gram matrices with RCCL inside libtlsqhip.so.
+value = ALM iterations completed in the K timed steps / wall time (max over ranks); ms_per_step = that wall time / K.
+N>1 row-shards the SAME 20000x512 problem (strong scaling) and exchanges the N x N Gram matrices with RCCL inside libtlsqhip.so.
+--dump-outputs DIR writes A, E (a seeded sample above 2^21 entries) and sv of the last timed solve as DIR/<name>.npy.
 
 Beside `value` (all outside the timed region):
   value_with_s          the same solve with the returned decomposition s = (U, S, Vt) of the last Z requested as well
@@ -38,6 +39,8 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 REF_PATH = os.path.join(ROOT, "tests", "golden", "bench_vectors.json")
+DUMP_MAX_ENTRIES = 1 << 21   # per dumped M x N output: 16 MB of float64 (A and E: 32 MB in all)
+DUMP_SEED = 20240
 
 
 def svp_hash(hist):
@@ -57,7 +60,14 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip value_with_s / value_host_pointers")
     ap.add_argument("--no-c5", action="store_true", help="skip the extra 65536x4096 fp32 measurement (extra.c5, one GPU only)")
     ap.add_argument("--timeout", type=float, default=900.0, help="seconds after which the run is declared hung (exit 3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed solve returned as DIR/<name>.npy (float64): A.npy and "
+                         "E.npy (the M x N outputs, row-major; above %d entries a fixed sample of that many entries, flat row-major "
+                         "indices numpy.random.default_rng(%d).choice(M*N, n, replace=False) sorted) and sv.npy (the rank, shape (1,))"
+                         % (DUMP_MAX_ENTRIES, DUMP_SEED))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # a collective that never completes must not hang the driver: the watchdog ends the process (no re-exec, no retry here)
     def hung():
@@ -213,6 +223,30 @@ def main():
     E = dE.cpu().numpy().T
     resid = float(np.linalg.norm(D[lo:hi] - (A + E)) / np.linalg.norm(D[lo:hi]))
     rel_a = float(np.linalg.norm(A - A0[lo:hi]) / np.linalg.norm(A0[lo:hi]))
+
+    # ---- --dump-outputs: A, E and sv of the last timed solve (dA, dE are overwritten by the solves below) -----------------
+    if args.dump_outputs:
+        if M * N <= DUMP_MAX_ENTRIES:
+            idx = np.arange(M * N, dtype=np.int64)
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(M * N, DUMP_MAX_ENTRIES, replace=False))
+        rows, cols = idx // N, idx % N
+        mine = (rows >= lo) & (rows < hi)
+        dumped = {}
+        for name, X in (("A", A), ("E", E)):
+            v = np.zeros(idx.size, dtype=np.float64)
+            v[mine] = X[rows[mine] - lo, cols[mine]]      # this rank's rows; the other entries come from their ranks
+            if use_dist:
+                t = torch.from_numpy(v).cuda()
+                dist.all_reduce(t, op=dist.ReduceOp.SUM)
+                v = t.cpu().numpy()
+            dumped[name] = v.reshape(M, N) if idx.size == M * N else v
+        dumped["sv"] = np.array([sv], dtype=np.float64)
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, v in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), v)
+
     # (one more solve WITH the per-iteration cost: the rank trajectory and the cost history the oracle's are compared with; the
     #  plain solves above settle cost < tol only - same iterations and outputs, tests/test_gpu_parity.py)
     _, rep_h, _ = eng.rpca_device(dD.data_ptr(), Ml, N, dA.data_ptr(), dE.data_ptr(), m_global=M, want_hist=True)

@@ -4,6 +4,11 @@ SURVEY.md §8c item (6): per-iteration cost and svp, the singular values of the 
 strided sample of A and E.  The inputs come from the seeded generator (a checksum of D guards against generator
 drift).  These are DATA produced by this repo's oracle, not by the reference (Julia cannot run here).
 
+The generator's low-rank product G1 G2 goes through BLAS, whose rounding depends on the CPU kernel and the thread count,
+so D's bits differ between machines.  tests/golden/oracle_inputs.npz therefore freezes the exact D as well: per case, the
+difference in ulps (int32, column-major) between D and `fixed_order_d`, a BLAS-free product that every machine rounds
+alike.  The test rebuilds D from it bit for bit and checks it against the checksum.
+
     python tests/golden/make_oracle_vectors.py
 """
 import hashlib
@@ -21,10 +26,26 @@ CASES = {"c1_500x50_r5": (500, 50, 5, 0), "c2s_2000x128_r8": (2000, 128, 8, 1)}
 STRIDE = 97
 
 
+def fixed_order_d(M, N, r, seed, S):
+    """G1 G2 + S with the factors of O.synth_lowrank_sparse (its first two draws) and the rank-one terms added in order
+    by elementwise numpy arithmetic (no BLAS, no FMA): the same bits on every machine.  Column-major."""
+    rng = np.random.default_rng(seed)
+    G1 = rng.standard_normal((M, r))
+    G2 = rng.standard_normal((r, N))
+    P = G1[:, :1] * G2[:1, :]
+    for k in range(1, r):
+        P = P + G1[:, k:k + 1] * G2[k:k + 1, :]
+    return np.asfortranarray(P + S)
+
+
 def main():
     out = {}
+    ulps = {}
     for name, (M, N, r, seed) in CASES.items():
-        D, _, _ = O.synth_lowrank_sparse(M, N, r, seed=seed)
+        D, _, S = O.synth_lowrank_sparse(M, N, r, seed=seed)
+        d = np.asfortranarray(D).view(np.int64) - fixed_order_d(M, N, r, seed, S).view(np.int64)
+        assert np.abs(d).max() < 2 ** 31
+        ulps[name] = d.ravel(order="F").astype(np.int32)
         A, E, s, sv, info = O.rpca(D)
         out[name] = {
             "M": M, "N": N, "rank": r, "seed": seed,
@@ -37,8 +58,10 @@ def main():
             "A_sample": [float(v) for v in A.ravel(order="F")[::STRIDE]],
             "E_sample": [float(v) for v in E.ravel(order="F")[::STRIDE]],
         }
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "oracle_vectors.json"), "w") as f:
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "oracle_vectors.json"), "w") as f:
         json.dump(out, f)
+    np.savez_compressed(os.path.join(here, "oracle_inputs.npz"), **ulps)
     print({k: (v["iters_done"], v["sv"]) for k, v in out.items()})
 
 

@@ -367,6 +367,57 @@ int tlsq_rpca_ga_f32(tlsq_handle h, const float* X, int64_t d, int64_t N, int64_
 int tlsq_ga_average_f64(tlsq_handle h, int average, double trim, const double* w, const double* U, int64_t d,
                         int64_t N, int64_t ldU, double* s, int memory);
 
+/* ---- flts: fast least trimmed squares, src/flts.jl ------------------------------------------------------------
+ * theta = argmin over h-subsets H of sum_{i in H} (a_i'theta - y_i)^2, by the reference's algorithm (Rousseeuw & Van Driessen
+ * 1999 as the reference implements it): nsub random p-subsets (extended while rank-deficient, :108-124), each followed by
+ * C-steps (:127-138).  The reference's optimize_H (:92-105) always restarts from the INITIAL theta, so every call of it performs
+ * exactly one distinct C-step whatever maxiter / dQmin are: all subsets get two C-steps, the 10 with the smallest Q (stable
+ * order) a third, and the smallest Q of those wins.  The library reproduces exactly that (maxiter and dQmin are validated and
+ * otherwise have no effect, as in the reference).  The p-subsets come from the library's own counter-based draw
+ * (tlsq_flts_subset), not from Julia's global RNG.  A is n x p (ldA, column-major), y has ny entries (ny != n: the reference's
+ * DimensionMismatch).  theta: p entries.  H (may be NULL): h row indices, 0-based, in the order of sortperm(abs.(r))[1:h].
+ * Q (may be NULL): the winner's objective.  p <= 64 (TLSQ_ERR_UNSUPPORTED above), n < 2^31.  A group handle
+ * (tlsq_create_multi) runs the call on its first GPU.  Errors: TLSQ_ERR_ARG (sizes, NULL, nsub < 10, maxiter < 1, h > n,
+ * a singular square p-subset when n <= p + 2), TLSQ_ERR_NONFINITE (Inf / NaN in A or y). */
+typedef struct tlsq_flts_opts {
+    int64_t h;          /* 0 -> resolved by tlsq_flts_resolve_h (:53-61) */
+    double  outliers;   /* -1: unset */
+    int64_t nsub;       /* N, >= 10; default 500 */
+    int32_t maxiter;    /* >= 1; default 100 (no effect on the result, see above) */
+    int32_t memory;     /* TLSQ_MEM_* for A, y, theta, H, Q */
+    double  dQmin;      /* default 1e-4 (no effect on the result) */
+    uint64_t seed;      /* the p-subset draws */
+} tlsq_flts_opts;
+/* Per-call report.  The pointers are optional caller arrays (NULL: not written). */
+typedef struct tlsq_flts_info {
+    int64_t h, p;
+    int64_t winner;                /* index (0..nsub-1) of the initial subset the winner grew from */
+    int64_t rank_extended_draws;   /* initial subsets whose p rows were rank deficient and were redrawn with more rows */
+    int64_t max_subset_rows;       /* the largest final draw */
+    int64_t csteps_done;           /* distinct C-steps computed: 2 nsub + 10 */
+    int64_t h_mismatch;            /* C-steps whose membership count differed from h (always 0) */
+    int64_t select_passes;         /* histogram passes over A of all radix selections */
+    double  chance;                /* 1-(1-(h/n)^p)^N, the reference's verbose estimate (:63) */
+    double  ms_total;
+    int64_t* subset_rows;          /* nsub: rows of the final draw of every initial subset */
+    double*  q_stage2;             /* nsub: Q after two C-steps */
+    int64_t* candidates;           /* 10: the subsets of the third stage, in stable Q order */
+    double*  q_final;              /* 10: their Q after the third C-step */
+} tlsq_flts_info;
+void tlsq_flts_opts_default(tlsq_flts_opts* o);
+/* The h rule of :53-61 (host only): returns which branch applied (0: the given h, 1: from outliers, 2: the default) or
+ * TLSQ_ERR_ARG (n < 1, p < 1, h_out NULL). Julia's round (ties to even). */
+int tlsq_flts_resolve_h(int64_t n, int64_t p, int64_t h, double outliers, int64_t* h_out);
+/* The draw the device makes for initial subset s, attempt a (host only): k distinct row indices of [0, n) into J, in draw
+ * order (Floyd's algorithm on a counter-based hash of (seed, s, attempt)).  flts draws attempt a with k = p + a rows. */
+int tlsq_flts_subset(uint64_t seed, int64_t s, int32_t attempt, int64_t n, int64_t k, int64_t* J);
+int tlsq_flts_f64(tlsq_handle h, const double* A, int64_t n, int64_t p, int64_t ldA, const double* y, int64_t ny,
+                  const tlsq_flts_opts* opts, double* theta, int64_t* H, double* Q, tlsq_flts_info* info);
+/* Float32 data: residuals, keys and subset selection in float as the reference computes them for Float32 arrays; moments and
+ * solves accumulate in double; theta is rounded to float. */
+int tlsq_flts_f32(tlsq_handle h, const float* A, int64_t n, int64_t p, int64_t ldA, const float* y, int64_t ny,
+                  const tlsq_flts_opts* opts, float* theta, int64_t* H, double* Q, tlsq_flts_info* info);
+
 /* ---- kernel-level entry points (DEVICE pointers; used by the parity tests and bench.py) -------
  * shrink sweep  (src/robustPCA.jl:188-192):  E = soft_th((D-A)+inv_mu*Y, thr) [max(E,0)]; Z=(D-E)+inv_mu*Y
  * update sweep  (src/robustPCA.jl:217-222):  [A=max(A,0)]; R=(D-A)-E; Y=Y+mu*R

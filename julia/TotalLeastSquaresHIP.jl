@@ -17,7 +17,7 @@ module TotalLeastSquaresHIP
 
 using LinearAlgebra, Libdl
 
-export rpca, lowrankfilter, hankel, unhankel, tls, tls!, rtls, rpca_ga, entrywise_median, entrywise_trimmed_mean, μ!
+export rpca, lowrankfilter, hankel, unhankel, tls, tls!, rtls, rpca_ga, entrywise_median, entrywise_trimmed_mean, μ!, flts
 
 const LIB = Ref{String}(get(ENV, "TLSQ_LIB", joinpath(@__DIR__, "..", "totalleastsquares.jl_amd", "libtlsqhip.so")))
 
@@ -466,6 +466,53 @@ function rpca_ga(X::AbstractMatrix{Float32}, r = minimum(size(X)), U = nothing; 
     end
     st == 1 && @warn "Reached maximum number of iterations"                                      # :306
     Q
+end
+
+# ---- flts (src/flts.jl) ----------------------------------------------------------------------------------------------------
+# mirrors `struct tlsq_flts_opts` (48 bytes) and `struct tlsq_flts_info` (112 bytes)
+mutable struct FltsOpts
+    h::Int64; outliers::Cdouble; nsub::Int64; maxiter::Int32; memory::Int32; dQmin::Cdouble; seed::UInt64
+    FltsOpts() = new()
+end
+mutable struct FltsInfo
+    h::Int64; p::Int64; winner::Int64; rank_extended_draws::Int64; max_subset_rows::Int64; csteps_done::Int64
+    h_mismatch::Int64; select_passes::Int64; chance::Cdouble; ms_total::Cdouble
+    subset_rows::Ptr{Int64}; q_stage2::Ptr{Cdouble}; candidates::Ptr{Int64}; q_final::Ptr{Cdouble}
+    FltsInfo() = new()
+end
+
+# The reference's signature and keywords.  The p-subsets are the library's counter-based draws, seeded from Julia's global
+# RNG (`rand(UInt64)`), so `Random.seed!` makes calls reproducible as in the reference.  H comes back 1-based.
+for (T, sym) in ((Float64, :tlsq_flts_f64), (Float32, :tlsq_flts_f32))
+    @eval function _flts(A::Matrix{$T}, y::Vector{$T}, h, outliers, N, maxiter, ΔQmin, return_set, verbose)
+        n, p = size(A)
+        o = FltsOpts(); ccall((:tlsq_flts_opts_default, LIB[]), Cvoid, (Ref{FltsOpts},), o)
+        o.h = h; o.outliers = outliers; o.nsub = N; o.maxiter = maxiter; o.dQmin = ΔQmin; o.seed = rand(UInt64); o.memory = MEM_HOST
+        info = FltsInfo(); info.subset_rows = C_NULL; info.q_stage2 = C_NULL; info.candidates = C_NULL; info.q_final = C_NULL
+        θ = Vector{$T}(undef, p); H = Vector{Int64}(undef, n); Q = Ref{Cdouble}(0)
+        check(ccall(($(QuoteNode(sym)), LIB[]), Cint,
+            (Ptr{Cvoid}, Ptr{$T}, Int64, Int64, Int64, Ptr{$T}, Int64, Ref{FltsOpts}, Ptr{$T}, Ptr{Int64}, Ref{Cdouble},
+             Ref{FltsInfo}), handle(), A, n, p, n, y, length(y), o, θ, H, Q, info))
+        return_set ? (H[1:info.h] .+ 1, θ, $T(Q[])) : θ
+    end
+end
+
+function flts(A::AbstractArray{<:Real}, y::AbstractVector{<:Real}; h::Integer = 0, outliers::Real = -1, N::Integer = 500,
+              maxiter::Integer = 100, ΔQmin::Real = 0.0001, return_set::Bool = false, verbose::Bool = false)
+    n = length(y)
+    size(A, 1) == n || throw(DimensionMismatch("Both inputs A and y should have the same number of rows"))
+    N >= 10 || throw(DomainError("N needs to be >= 10"))
+    p = ndims(A) == 2 ? size(A, 2) : 1
+    if verbose
+        hr = Ref{Int64}(0)
+        rule = ccall((:tlsq_flts_resolve_h, LIB[]), Cint, (Int64, Int64, Int64, Cdouble, Ref{Int64}), n, p, h, outliers, hr)
+        hv = hr[]
+        rule == 2 ? (@info "h was set to default: h = $hv. Breakdown point is at ~$(round(100 - hv / n * 100))% outliers") :
+                    (@info "h was set to: h = $hv. Breakdown point is at ~$(round(100 - hv / n * 100))% outliers")
+        @info "Chance to find an outlier-free p subset is at least ~$((1-(1-(hv/n)^p)^N) * 100) %"
+    end
+    F = eltype(A) === Float32 && eltype(y) === Float32 ? Float32 : Float64
+    _flts(Matrix{F}(reshape(A, n, p)), Vector{F}(y), h, outliers, N, maxiter, ΔQmin, return_set, false)
 end
 
 # other real element types (the reference is generic): computed in Float64 on the device, returned in the input's float type

@@ -8,7 +8,7 @@ from . import workloads  # noqa: F401
 from ._lib import dev_set, dev_from_env, dev_switches  # noqa: F401
 from .engine import (SVD, Engine, TlsqError, default_engine, hankel, ishankel, lowrankfilter, rpca,  # noqa: F401
                      rtls, soft_hankel_, tls, tls_, unhankel, rpca_ga, mu_, entrywise_trimmed_mean,
-                     entrywise_median)
+                     entrywise_median, flts)
 
 __all__ = ["SVD", "Engine", "TlsqError", "default_engine", "hankel", "ishankel", "lowrankfilter", "rpca",
-           "rtls", "soft_hankel_", "tls", "tls_", "unhankel", "rpca_ga", "mu_", "entrywise_trimmed_mean", "entrywise_median"]
+           "rtls", "soft_hankel_", "tls", "tls_", "unhankel", "rpca_ga", "mu_", "entrywise_trimmed_mean", "entrywise_median", "flts"]

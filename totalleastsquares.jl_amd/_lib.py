@@ -67,6 +67,19 @@ class GaInfo(C.Structure):
                 ("ms_total", C.c_double), ("ms_loop", C.c_double), ("passes", C.c_int64)]
 
 
+class FltsOpts(C.Structure):
+    _fields_ = [("h", C.c_int64), ("outliers", C.c_double), ("nsub", C.c_int64), ("maxiter", C.c_int32), ("memory", C.c_int32),
+                ("dQmin", C.c_double), ("seed", C.c_uint64)]
+
+
+class FltsInfo(C.Structure):
+    _fields_ = [("h", C.c_int64), ("p", C.c_int64), ("winner", C.c_int64), ("rank_extended_draws", C.c_int64),
+                ("max_subset_rows", C.c_int64), ("csteps_done", C.c_int64), ("h_mismatch", C.c_int64),
+                ("select_passes", C.c_int64), ("chance", C.c_double), ("ms_total", C.c_double),
+                ("subset_rows", C.POINTER(C.c_int64)), ("q_stage2", C.POINTER(C.c_double)),
+                ("candidates", C.POINTER(C.c_int64)), ("q_final", C.POINTER(C.c_double))]
+
+
 # every symbol include/tlsq.h declares (tests check that the .so exports all of them)
 EXPORTS = [
     "tlsq_version", "tlsq_dev_set", "tlsq_rpca_opts_default", "tlsq_create", "tlsq_create_multi", "tlsq_ngpus", "tlsq_destroy", "tlsq_last_error",
@@ -82,6 +95,7 @@ EXPORTS = [
     "tlsq_k_zsweep_f64", "tlsq_k_zsweep_gram_f64", "tlsq_k_zsweep_wide_f32", "tlsq_k_final_e_f64", "tlsq_k_matfun_sign_f64", "tlsq_k_matfun_invsqrt_f64", "tlsq_k_rr_small_f64",
     "tlsq_k_gram_f64", "tlsq_k_gram_f32", "tlsq_k_op_gram_f32", "tlsq_k_gemm_nn_f64", "tlsq_k_gemm_nt_f64", "tlsq_k_symeig_f64", "tlsq_k_symeig_chol_f64",
     "tlsq_k_opnorm_f64", "tlsq_k_maxabs_f64", "tlsq_k_tsqr_f64", "tlsq_k_svd_r_f64",
+    "tlsq_flts_opts_default", "tlsq_flts_resolve_h", "tlsq_flts_subset", "tlsq_flts_f64", "tlsq_flts_f32",
 ]
 
 _lib = None
@@ -170,10 +184,16 @@ def load():
     lib.tlsq_k_svd_r_f64.argtypes = [vp, vp, i64, i64, i64, vp, vp, i64, P(i64)]
     lib.tlsq_k_opnorm_f64.argtypes = [vp, vp, i64, i64, i64, P(dbl)]
     lib.tlsq_k_maxabs_f64.argtypes = [vp, vp, i64, P(dbl)]
+    lib.tlsq_flts_opts_default.argtypes = [P(FltsOpts)]
+    lib.tlsq_flts_opts_default.restype = None
+    lib.tlsq_flts_resolve_h.argtypes = [i64, i64, i64, dbl, P(i64)]
+    lib.tlsq_flts_subset.argtypes = [C.c_uint64, i64, C.c_int32, i64, i64, P(i64)]
+    lib.tlsq_flts_f64.argtypes = [vp, vp, i64, i64, i64, vp, i64, P(FltsOpts), vp, vp, vp, P(FltsInfo)]
+    lib.tlsq_flts_f32.argtypes = lib.tlsq_flts_f64.argtypes
     for name in EXPORTS:
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         if name not in ("tlsq_version", "tlsq_last_error", "tlsq_stream", "tlsq_rpca_opts_default",
-                        "tlsq_ga_opts_default"):
+                        "tlsq_ga_opts_default", "tlsq_flts_opts_default"):
             fn.restype = C.c_int
     _lib = lib
     return lib

@@ -191,6 +191,7 @@ enum WsSlot {
     WS_SL_BUF, WS_SL_TAB,   // spectrum slicer in front of the accurate route's Jacobi (sliced.hip): N x N iterates, block-pair table
     WS_LZX,   // granule buffers of k_lanczos_multi (lanczos.hip): written by nothing else
     WS_UPOL, WS_UPB,   // orthonormal polish of the derived singular vectors (solver.hip): second M x d panel, d x d Gram + correction
+    WS_FL_A, WS_FL_Y, WS_FL_TH, WS_FL_INIT, WS_FL_SEL, WS_FL_HIST, WS_FL_CAND, WS_FL_PART, WS_FL_MOM, WS_FL_MISC, WS_FL_SORT,   // flts (flts.hip)
     WS_COUNT
 };
 

@@ -634,6 +634,58 @@ class Engine:
                        "ms_loop": float(info.ms_loop), "ms_total": float(info.ms_total), "passes": int(info.passes)}
         return Q
 
+    def flts(self, A, y, *, h=0, outliers=-1, N=500, maxiter=100, dQmin=1e-4, return_set=False, seed=0, verbose=False,
+             return_report=False):
+        """flts(A, y; h, outliers, N, maxiter, ΔQmin, return_set, verbose) (src/flts.jl:42-89) on the GPU.  A is a vector
+        (p = 1) or an n x p matrix; float32 data take the fp32 entry.  Returns θ, or (H, θ, Q) with H 0-based in
+        sortperm order.  The p-subsets are the library's seeded draws (`seed`), not Julia's global RNG."""
+        Aa, ya = np.asarray(A), np.asarray(y)
+        f32 = Aa.dtype == np.float32 and ya.dtype == np.float32
+        dt = np.float32 if f32 else np.float64
+        if Aa.ndim == 1:
+            Aa = Aa.reshape(-1, 1)
+        Af = _f(Aa, dt)
+        yf = np.ascontiguousarray(ya, dtype=dt).reshape(-1)
+        n, p = Af.shape
+        o = L.FltsOpts()
+        self.lib.tlsq_flts_opts_default(C.byref(o))
+        o.h, o.outliers, o.nsub, o.maxiter = int(h), float(outliers), int(N), int(maxiter)
+        o.dQmin, o.seed = float(dQmin), int(seed)
+        if verbose:
+            hh = C.c_int64()
+            rule = self.lib.tlsq_flts_resolve_h(n, p, int(h), float(outliers), C.byref(hh))
+            if rule >= 0:
+                hv = int(hh.value)
+                bd = _julia_round(100 - hv / n * 100)
+                print(f"[ Info: h was set to{' default' if rule == 2 else ''}: h = {hv}. Breakdown point is at ~{bd}% outliers")
+                print(f"[ Info: Chance to find an outlier-free p subset is at least ~{(1 - (1 - (hv / n) ** p) ** int(N)) * 100} %")
+        theta = np.zeros(p, dtype=dt)
+        Q = C.c_double(0.0)
+        nsub = max(int(N), 1)
+        rows = np.zeros(nsub, dtype=np.int64)
+        q2 = np.zeros(nsub)
+        cand = np.zeros(10, dtype=np.int64)
+        qf = np.zeros(10)
+        info = L.FltsInfo()
+        if return_report:
+            info.subset_rows = rows.ctypes.data_as(C.POINTER(C.c_int64))
+            info.q_stage2 = q2.ctypes.data_as(C.POINTER(C.c_double))
+            info.candidates = cand.ctypes.data_as(C.POINTER(C.c_int64))
+            info.q_final = qf.ctypes.data_as(C.POINTER(C.c_double))
+        hmax = max(n, 1)
+        H = np.zeros(hmax, dtype=np.int64) if (return_set or return_report) else None
+        fn = self.lib.tlsq_flts_f32 if f32 else self.lib.tlsq_flts_f64
+        self._check(fn(self.h, _ptr(Af), n, p, n, _ptr(yf), yf.shape[0], C.byref(o), _ptr(theta),
+                       _ptr(H) if H is not None else None, C.byref(Q), C.byref(info)))
+        hv = int(info.h)
+        out = (H[:hv].copy(), theta, float(Q.value)) if return_set else theta
+        if return_report:
+            rep = {k: getattr(info, k) for k, _ in L.FltsInfo._fields_ if not k.startswith(("subset_rows", "q_stage2", "candidates",
+                                                                                            "q_final"))}
+            rep.update(subset_rows=rows, q_stage2=q2, candidates=cand, q_final=qf, H=H[:hv].copy(), Q=float(Q.value))
+            return out, rep
+        return out
+
     def _average(self, code, s, w, U, P=float("nan")):
         Uf = _f(U)
         d, N = Uf.shape
@@ -672,6 +724,11 @@ def ishankel(A):
 
 
 _default = None
+
+
+def _julia_round(x):
+    """Julia's round (ties to even) as a Float64, printed like Julia prints it"""
+    return float(round(x))
 
 
 def default_engine() -> Engine:
@@ -727,3 +784,7 @@ def entrywise_median(s, w, U):
 
 def rtls(A, y, **kw):
     return default_engine().rtls(A, y, **kw)
+
+
+def flts(A, y, **kw):
+    return default_engine().flts(A, y, **kw)

@@ -157,4 +157,4 @@ def test_report_reads_the_info_struct_on_first_use():
         tlsq_amd.dev_set(name, "1")
         tlsq_amd.dev_set(name, None)
     with pytest.raises(Exception):
-        tlsq_amd.dev_set("NO_FUSED_SWEEP", "1")   # an ablation switch: refused by the shipped library
+        tlsq_amd.dev_set("NO_FUSED_SWEEP", "1")   # not a switch (a removed ablation path): an unknown name

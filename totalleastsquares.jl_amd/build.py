@@ -35,7 +35,7 @@ def build(force=False, verbose=True):
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "internal.hpp"), os.path.join(CSRC, "svdstep.hpp"),
                os.path.join(ROOT, "include", "tlsq.h")]
-    extra = os.environ.get("TLSQ_EXTRA_FLAGS", "").split()   # development builds (tools/kbench.py ablations)
+    extra = os.environ.get("TLSQ_EXTRA_FLAGS", "").split()   # extra hipcc flags for development builds (e.g. -Rpass-analysis)
     force = force or bool(extra)
     objs = []
     procs = []

@@ -187,8 +187,7 @@ static int lowrankfilter_impl(tlsq_handle h, const T* y, int64_t Nx, int64_t Dch
     // ... and neither is A (one channel, lag 1): the loop keeps it in factors, the anti-diagonal means are taken from them
     // (unhankel_factors), and the panel only exists if some iteration needed it in memory (rank above 32): four resident
     // panels (E, Y, Z, R)
-    const bool factors_ok = !dev_is(DEV_UNHANKEL_FACTORS, '0');
-    const bool factors_out = lazy && !sharded && factors_ok && Dch == 1 && lag == 1 && (size_t)n * 32 * 8 <= 64 * 1024;
+    const bool factors_out = lazy && !sharded && Dch == 1 && lag == 1 && (size_t)n * 32 * 8 <= 64 * 1024;
     // The plain truncation branch (sv > 0, :123-126) on the series itself (round 6, hankelop.hip): the Gram matrix of H from n
     // lagged autocorrelation sums, the factor H V[:, 1:sv] as sv FIR filters, the anti-diagonal means from the factors - neither H
     // nor A is ever stored (one channel, lag 1, one GPU; otherwise the panels as before).  HANKEL_STRUCT=0: the panel form.

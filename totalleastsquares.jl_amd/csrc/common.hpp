@@ -110,10 +110,9 @@ int ws_get(Handle* h, int slot, size_t bytes, void** out);
 
 // ---- development switches (runtime.hip) ---------------------------------------------------------------------------
 // Every alternative HIP path the library can be told to take is one entry of this list.  Values are
-// set through tlsq_dev_set(name, value) - the tests and tools call it; a name that is not on the list is an error - and,
-// only in a build with -DTLSQ_DEV_SWITCHES, from environment variables TLSQ_<NAME> read once at the first tlsq_create.
-// The shipped build reads no environment variable at all: a leaked or mistyped variable cannot change which solver runs.
-#define TLSQ_DEV_LIST_LIVE(X)                                                                                             \
+// set through tlsq_dev_set(name, value) only - the tests and tools call it; a name that is not on the list is an error.
+// The library reads no environment variable at all: a leaked or mistyped variable cannot change which solver runs.
+#define TLSQ_DEV_LIST(X)                                                                                                  \
     X(DEBUG) X(DEBUG_HASH) X(PHASE_TIMING) X(WS_POISON) X(FORCE_COMM) X(FORCE_LOCALGROUP) X(FAIL_RANK) X(NO_ZSWEEP)   \
     X(FUSED_REBUILD) X(RUS_ROWS) X(RUS_CT) X(SWEEP_GRID) X(RSKIP_MARGIN) X(MATFUN_DEFL) X(NO_QUINTIC)                 \
     X(NO_CERT_ASYNC) X(FAIL_CERT_AT) X(NO_SPEC_REBUILD) X(CERT_EARLY) X(CERT_PRIO) X(NO_SMALL_MM) X(COLD_Q)           \
@@ -121,33 +120,11 @@ int ws_get(Handle* h, int slot, size_t bytes, void** out);
     X(FUSED_ZGRAM_MINROWS) X(FUSED_ABLATE) X(FUSED_ZGRAM_N512) X(OPGRAM_OLD) X(OPGRAM_H3) X(GRAM_H3)                  \
     X(NO_WIDE_SWEEP) X(NO_SLICED_EIG) X(SLICE_NORMWISE) X(HANKEL_STRUCT) X(SLICE_TARGET) X(COLD_TOP) X(COLD_TOL0)         \
     X(LZ_MULTI) X(RITZ_SORT) X(PAD_PROJECT) X(HOST_TRACE) X(SWEEP_TIMING_STRIDE) X(SLICE_MIDJ)
-// Ablation switches: every one of them selects a path that was measured against its successor and is kept for that comparison
-// (docs/HISTORY.md).  No committed test or tool uses them; the SHIPPED library does not accept them - 
-// tlsq_dev_set answers TLSQ_ERR_ARG as for an unknown name, so dev_get() of these is always "not set" - only a build with
-// -DTLSQ_DEV_SWITCHES (TLSQ_EXTRA_FLAGS of the build recipe) does.  48 live switches, 65 ablation switches.
-#define TLSQ_DEV_LIST_ABLATION(X)                                                                                         \
-    X(NO_FUSED_SWEEP) X(NO_FIRST_SHRINK) X(NO_FUSED_REBUILD) X(NO_REBUILD_STORE)                                      \
-    X(NO_MAX_BOUND) X(LAST_GUESS) X(NO_POWER_LB) X(NO_POWER_START) X(POWER_LEVELS) X(FULL_EIG) X(NO_GRAM_DENSE)       \
-    X(NO_MATFUN_ROUTE) X(MATFUN_SYM) X(MATFUN_COND) X(NO_DEFLATED_CERT) X(NO_DEEP_POWERS) X(NO_POWER_CERT)            \
-    X(NO_CERT_OVERLAP) X(NO_DEFLATED_SVD) X(NO_FUSED_DEFLATE) X(NO_RR_FAST) X(NO_RR_BLOCKED) X(NO_U_POLISH)           \
-    X(NO_GX_REUSE) X(COLD_CGS2) X(NO_ONEPASS) X(NO_CHOLQR) X(NO_BLOCKED_CGS2) X(JACOBI2) X(NO_JACOBI_REG)             \
-    X(JACOBI_RPL) X(NO_CHOL) X(NO_SYMM_MFMA) X(GRAM_OLD) X(GRAM_RHO) X(GRAM_SPLIT) X(GRAM_ROWWISE) X(GRAM_F32MFMA)    \
-    X(GEMM_WGS) X(HOOK_SKETCH) X(NO_F32_SKINNY) X(OVERLAP_CHUNKS) X(OVERLAP_LDS) X(OVERLAP_NOPRIO) X(NO_TSMM)         \
-    X(NO_TSMM_SELV) X(TSMM_MAXR) X(NO_TSMM_SEL) X(UNHANKEL_FACTORS) X(GA_BLOCKS) X(GA_SOLO) X(NO_FUSED_GR)            \
-    X(NO_HOOK_ZQ) X(GRAM_H3_FOLD) X(HOOK_CLASSIC) X(HOOK_POWER) X(HOOK_COLD) X(HOOK_CGS2) X(HOOK_ORTH_ALL)            \
-    X(HOOK_PAD_REFRESH) X(COLD_GROW) X(SLICE_SCHED) X(SLICE_LEVELS) X(SLICE_L0) X(NO_MAXABS_ASYNC)
-#define TLSQ_DEV_LIST(X) TLSQ_DEV_LIST_LIVE(X) TLSQ_DEV_LIST_ABLATION(X)
 enum DevKey {
 #define TLSQ_DEV_ENUM(n) DEV_##n,
     TLSQ_DEV_LIST(TLSQ_DEV_ENUM)
 #undef TLSQ_DEV_ENUM
     DEV_COUNT
-};
-// the first DEV_LIVE_COUNT keys are the live ones
-enum { DEV_LIVE_COUNT = 0
-#define TLSQ_DEV_ONE(n) +1
-    TLSQ_DEV_LIST_LIVE(TLSQ_DEV_ONE)
-#undef TLSQ_DEV_ONE
 };
 const char* dev_get(DevKey k);   // the value as a string, nullptr when the switch is not set
 inline bool dev_is(DevKey k, char c) {
@@ -156,7 +133,6 @@ inline bool dev_is(DevKey k, char c) {
 }
 // name with or without the TLSQ_ prefix; value == nullptr clears the switch.  TLSQ_ERR_ARG for a name not on the list.
 int dev_set(const char* name, const char* value);
-void dev_load_env();             // (no-op unless built with -DTLSQ_DEV_SWITCHES)
 void host_mark(const char* tag);   // HOST_TRACE=1: a wall-clock mark of the host side of the call (runtime.hip)
 void host_trace_dump();
 // DEBUG_HASH=1: "[hash] <tag> <64-bit FNV-1a of the buffer>" on stderr after a stream synchronisation - two runs of the same
@@ -220,9 +196,6 @@ template <typename T>
 int launch_update_shrink(Handle* h, const T* D, T* A, const T* E, T* Y, T* R, T* En, T* Zn, int64_t n, T mu,
                          int nonnegA, T inv_mu_n, T thr_n, int nonnegE, double* sumsq = nullptr,
                          double* zero_slots = nullptr);   // zero_slots: 64 doubles cleared for the next sweep
-// Y = D / s  (src/robustPCA.jl:181), contiguous n
-template <typename T>
-int launch_div_scalar(Handle* h, const T* D, T* Y, int64_t n, T s);
 // out[0] = max |x_i|  (device scalar, as double bits in a uint64 slot)
 template <typename T>
 int launch_maxabs(Handle* h, const T* x, int64_t n, double* host_out);
@@ -265,7 +238,6 @@ int launch_rebuild_update_shrink(Handle* h, const T* D, const double* Tm, const 
                                  T* En, T* Zn, int64_t M, int64_t N, int64_t r, T mu, int nonnegA, T inv_mu_n, T thr_n,
                                  int nonnegE, double* sumsq, double* zero_slots = nullptr, const T* hankel_y = nullptr,
                                  int64_t hankel_K = 0, int64_t row0 = 0, int64_t row1 = 0,   // rows [row0, row1), default all
-                                 size_t pad_lds = 0,   // unused dynamic LDS per workgroup (caps the residency per CU)
                                  HankelGeom hg = HankelGeom());
 // A (M x N, ld M) = Tm Vs' (Tm M x r fp64, Vs N x r): the streaming-store form of the rebuild (r <= 32, even M)
 template <typename T>

@@ -664,8 +664,8 @@ __global__ __launch_bounds__(512) void k_gram_kc(const TZ* __restrict__ Z, int64
 int gram_plan(Handle* h, int z_f32, int64_t N, int64_t K, int nchunks, GramPlan* pl) {
     const int64_t nti = (N + TI - 1) / TI, noff = nti * (nti - 1) / 2;
     // relative cost of a diagonal work item per row of Z (9 of 16 MFMA tiles per SIMD + the shared per-stage overhead)
-    const double rho = [] { const char* e = dev_get(DEV_GRAM_RHO); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 0.62; }();
-    const int64_t target_wgs = [] { const char* e = dev_get(DEV_GEMM_WGS); const long v = e ? atol(e) : 0; return (int64_t)(v > 0 ? v : 256); }();
+    constexpr double rho = 0.62;
+    constexpr int64_t target_wgs = 256;   // one workgroup per CU
     // K splits (nsplit_o for the off-diagonal tiles, nsplit_d for the diagonal ones) by a small cost model, in us:
     // an item of kc rows takes kc * c_row (a CU at ~92 % of its MFMA peak: 2 * 128 * 128 flop per row) + c_item
     // (dispatch, first loads, slab store: fitted), items run in rounds of one per CU, and every slab entry is written and read once more
@@ -722,13 +722,6 @@ int gram_plan(Handle* h, int z_f32, int64_t N, int64_t K, int nchunks, GramPlan*
         }
         if (noff == 0 && so >= hi) break;
     }
-    if (const char* e = dev_get(DEV_GRAM_SPLIT)) {   // development: "o,d"
-        long o = 0, d = 0;
-        if (sscanf(e, "%ld,%ld", &o, &d) == 2 && o > 0 && d > 0) {
-            nsplit_o = noff > 0 ? std::min<int64_t>(o, maxsplit) : 1;
-            nsplit_d = std::min<int64_t>(d, maxsplit);
-        }
-    }
     const int64_t kchunk_o = chunk_of(nsplit_o, TK), kchunk_d = chunk_of(nsplit_d, DTK);
     {
         const bool dbg = dev_is(DEV_DEBUG, '2');
@@ -747,8 +740,7 @@ int gram_plan(Handle* h, int z_f32, int64_t N, int64_t K, int nchunks, GramPlan*
     // 32 tiles); blocks of 8 x 4 tiles share 12.  From N = 2048 on the kernel is otherwise bound by that traffic
     // (65536 x 4096: 70 GB per Gram).
     const int32_t* order = nullptr;
-    const bool no_order = dev_is(DEV_GRAM_ROWWISE, '1');
-    if (nti > 8 && !no_order) {
+    if (nti > 8) {
         void* tab;
         TLSQ_TRY(ws_get(h, WS_GRAMTAB, (size_t)noff * 8, &tab));
         if (h->gram_tab_nti != nti) {
@@ -932,17 +924,12 @@ int gemm_mixed(Handle* h, bool A_KC, bool B_KC, const void* A, int a_f32, int64_
                const double* skip, double* normpart, int* normblocks) {
     if (P <= 0 || Q <= 0) return TLSQ_OK;
     if (normpart && !symmetric) return set_err(h, TLSQ_ERR_ARG, "gemm: the norm by-product needs the symmetric (slab) path");
-    const bool old_gram = dev_is(DEV_GRAM_OLD, '1');
-    if (symmetric && A_KC && B_KC && A == B && lda == ldb && a_f32 == b_f32 && !c_f32 && P == Q && !old_gram)
+    if (symmetric && A_KC && B_KC && A == B && lda == ldb && a_f32 == b_f32 && !c_f32 && P == Q)
         return gram_kc(h, A, a_f32, lda, (double*)C, ldc, P, K, skip, normpart, normblocks);   // the Gram matrix of one operand
     const int64_t nti = (P + TI - 1) / TI, ntj = (Q + TJ - 1) / TJ;
     const int64_t tiles = symmetric ? nti * (nti + 1) / 2 : nti * ntj;
     // split K so that the launch has ~256 workgroups (one per CU), each with >= 4 K stages
-    const int64_t target_wgs = [] {
-        const char* e = dev_get(DEV_GEMM_WGS);
-        const long v = e ? atol(e) : 0;
-        return (int64_t)(v > 0 ? v : 256);   // one workgroup per CU (512 and 768 measured the same on C2)
-    }();
+    constexpr int64_t target_wgs = 256;   // one workgroup per CU (512 and 768 measured the same on C2)
     int64_t nsplit = 1;
     // skinny outputs (P <= 32 rows of MFMA work per tile) are bandwidth/latency bound, not MFMA bound: they want
     // several workgroups per CU in flight, so split K further
@@ -1452,9 +1439,7 @@ int gram_any(Handle* h, const void* Z, int z_f32, int64_t M, int64_t N, int64_t 
         return TLSQ_OK;
     }
     // fp32 panels in large mode (no dense eigen-solver behind the count anyway): the fp32 MFMA with fp64 fold-in
-    const bool no_f32mfma = dev_is(DEV_GRAM_F32MFMA, '0');
-    const bool all_f32mfma = dev_is(DEV_GRAM_F32MFMA, '2');
-    if (z_f32 && (mfma32 == 1 || (mfma32 < 0 && !no_f32mfma && (N > 2048 || all_f32mfma))))
+    if (z_f32 && (mfma32 == 1 || (mfma32 < 0 && N > 2048)))
         return gram_f32mfma(h, (const float*)Z, ldZ, G, ldG, N, M);
     return gemm_mixed(h, true, true, Z, z_f32, ldZ, Z, z_f32, ldZ, G, 0, ldG, N, N, M, true);
 }
@@ -1654,7 +1639,7 @@ static int tsmm_impl(Handle* h, const void* Z, int z_f32, int64_t ldz, const dou
     if (r > 96) return set_err(h, TLSQ_ERR_ARG, "tsmm: r > 96");
     const int nct = (int)((r + 15) / 16);
     const int lw = 16 * nct;
-    if (!W && (K & 3) == 0 && nct <= 2 && !dev_is(DEV_NO_TSMM_SELV, '1')) {
+    if (!W && (K & 3) == 0 && nct <= 2) {
         const bool tall = M >= 65536;
         const dim3 grid((unsigned)((M + (tall ? 64 : 32) - 1) / (tall ? 64 : 32)));
 #define TSV_LAUNCH(TA, NC, RTT)                                                                                     \

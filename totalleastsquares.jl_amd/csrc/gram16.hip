@@ -36,7 +36,7 @@ constexpr int HK = 64;                // rows per stage = two 16 x 16 x 32 steps
 constexpr int HP = 64;                // halfs per staged column (128 bytes: the stage's eight 16-byte row groups, swizzled - h3_sw)
 constexpr int HPANEL = HT * HP;       // halfs per plane of a panel (16 KB)
 constexpr int HBUF = 4 * HPANEL;      // A hi, A lo, B hi, B lo (64 KB)
-// (fp64 fold-in: template parameter of the kernel - every stage or every 2 or 4 stages = 64, 128, 256 rows; GRAM_H3_FOLD, default 128)
+constexpr int HFOLD = 2;              // stages per fp64 fold-in: every 128 rows (64 and 256 were measured as well)
 
 __global__ __launch_bounds__(256) void k_absmax_bits(const float* __restrict__ Z, int64_t n, unsigned int* __restrict__ out) {
     const int64_t nv = n / 4;
@@ -98,7 +98,6 @@ __global__ __launch_bounds__(256) void k_split_f16(const float* __restrict__ Z, 
 // conflicts on three columns of every group.  The stores (eight lanes per column) stay conflict-free under any such swizzle.
 __device__ __forceinline__ int h3_sw(int c) { return (c >> 1) & 7; }
 
-template <int HFOLD>
 // (one workgroup per CU: 128 KB of stage buffers; the (512, 2) bound of round 5 only capped the registers - same time)
 __global__ __launch_bounds__(512, 1) void k_gram_h3(const _Float16* __restrict__ H, const _Float16* __restrict__ L, int64_t ld,
                                                     double* __restrict__ slab, int64_t N, int64_t K, int64_t kchunk,
@@ -310,18 +309,9 @@ int gram_h3(Handle* h, const float* Z, int64_t ld, double* G, int64_t ldg, int64
     TLSQ_TRY(gram_tile_table(h, nti, &tab));
     const int64_t nwork = ntiles * nsplit, cpx = (nwork + 7) / 8;
     const size_t lds = (size_t)2 * HBUF * 2;
-    const int fold = [] { const char* e = dev_get(DEV_GRAM_H3_FOLD); const int v = e ? atoi(e) : 2; return v == 1 || v == 4 ? v : 2; }();   // stages of 64 rows
-#define H3_LAUNCH(F)                                                                                                             \
-    do {                                                                                                                         \
-        TLSQ_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_gram_h3<F>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        (int)lds));                                                                              \
-        hipLaunchKernelGGL(k_gram_h3<F>, dim3((unsigned)(8 * cpx)), dim3(512), lds, h->stream, (const _Float16*)hp,              \
-                           (const _Float16*)lp, ld, (double*)slab, N, K, kchunk, slab_stride, (int)ntiles, (int)nsplit, tab);    \
-    } while (0)
-    if (fold == 1) H3_LAUNCH(1);
-    else if (fold == 4) H3_LAUNCH(4);
-    else H3_LAUNCH(2);
-#undef H3_LAUNCH
+    TLSQ_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_gram_h3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_gram_h3, dim3((unsigned)(8 * cpx)), dim3(512), lds, h->stream, (const _Float16*)hp, (const _Float16*)lp, ld,
+                       (double*)slab, N, K, kchunk, slab_stride, (int)ntiles, (int)nsplit, tab);
     ++h->kern_gram_h3;
     hipLaunchKernelGGL(k_h3_reduce, dim3(2048), dim3(256), 0, h->stream, (const double*)slab, slab_stride, (int)nsplit,
                        (const double*)sc, G, ldg, (int)N);

@@ -732,10 +732,8 @@ inline int pass_blocks(int64_t N, int64_t d) {
     int64_t nb = (N + gpb * 8 - 1) / (gpb * 8);   // >= 8 columns per lane group
     // two blocks per CU: measured best for every column length (256 / 1024 / 2048 / 4096 blocks are slower) — each
     // block costs a partial row in k_ga_reduce, and the columns in flight per lane group already cover the latency
-    const int env_cap = [] { const char* e = dev_get(DEV_GA_BLOCKS); return e ? atoi(e) : 0; }();   // tuning knob
-    const int64_t cap = env_cap > 0 ? env_cap : 512;
     if (nb < 1) nb = 1;
-    if (nb > cap) nb = cap;
+    if (nb > 512) nb = 512;
     return (int)nb;
 }
 
@@ -1180,9 +1178,8 @@ int tlsq_rpca_ga_f64(tlsq_handle h, const double* X, int64_t d, int64_t N, int64
     const double t_begin = now_ms();
     const int hist_cap = (info && info->dq_hist && info->hist_capacity > 0)
                              ? (int)std::min<int64_t>(info->hist_capacity, iters) : 0;
-    // small problems run in one workgroup (k_ga_solo); TLSQ_GA_SOLO=0 sends them through the grid path as well
-    const bool solo_on = !dev_is(DEV_GA_SOLO, '0');
-    const bool solo = solo_on && mode == TLSQ_GA_MEAN && !h->comm && d <= 64 && N * (d + 1) <= 18000;
+    // small problems run in one workgroup (k_ga_solo)
+    const bool solo = mode == TLSQ_GA_MEAN && !h->comm && d <= 64 && N * (d + 1) <= 18000;
     GaBuffers b;
     // (a caller's average: buffers of the plain mean - w, q, sbuf, state are all it needs)
     if (!solo) TLSQ_TRY(ga_alloc(h, d, N, cb_mode ? TLSQ_GA_MEAN : mode, hist_cap, true, &b));

@@ -1173,8 +1173,7 @@ int symeig_f64(Handle* h, const double* G, int64_t N, int64_t ldG, double* B, do
         // one half-wave per column pair; whole waves only
         const int npair0 = (int)((N + 1) / 2);
         const int nthr0 = ((npair0 * 32 + 63) / 64) * 64;
-        const bool no_two = dev_is(DEV_JACOBI2, '0');
-        if (want_v && two_sided && !no_two)
+        if (want_v && two_sided)
             hipLaunchKernelGGL(k_jacobi2_small<true>, dim3(1), dim3(nthr0), 0, h->stream, G, ldG, B, V, lam_dev,
                                (int)N, tol0, (double)N * eps0, max_sweeps0, sweeps_dev);
         else if (want_v)
@@ -1342,7 +1341,6 @@ static int jr_run_sweeps(Handle* h, double* B, int64_t N, double tol_r, const do
     bool converged = false;
     int sweep = 0;
     TLSQ_HIP(h, hipMemsetAsync(rot, 0, 48, h->stream));   // rotation count, largest |tan|, sweeps_dev (unused here), state
-    const bool one = dev_is(DEV_JACOBI_RPL, '1');   // (JACOBI_RPL=1: one row per lane, the first form: 8 / 16 waves)
     const int rounds = tab_dev ? nrounds : nblk - 1;
     const int64_t R = rows > 0 ? rows : N;   // rows a workgroup has to cover
     while (sweep < max_sweeps && !converged) {
@@ -1352,23 +1350,17 @@ static int jr_run_sweeps(Handle* h, double* B, int64_t N, double tol_r, const do
                 const int grid = tab_dev ? round_cnt[r] : nblk / 2;
                 if (grid <= 0) continue;
                 const JrPair* tab = tab_dev ? tab_dev + round_off[r] : nullptr;
-                if (R <= 128 && !one)
+                if (R <= 128)
                     hipLaunchKernelGGL((k_jacobi_reg<1, 2>), dim3(grid), dim3(64), 0, h->stream, B, (int)N, nblk, r, tol_r, params, rot,
                                        (const int*)state, tab);
-                else if (R <= 256 && !one)
+                else if (R <= 256)
                     hipLaunchKernelGGL((k_jacobi_reg<2, 2>), dim3(grid), dim3(128), 0, h->stream, B, (int)N, nblk, r, tol_r, params, rot,
                                        (const int*)state, tab);
-                else if (R <= 512 && !one)
+                else if (R <= 512)
                     hipLaunchKernelGGL((k_jacobi_reg<4, 2>), dim3(grid), dim3(256), 0, h->stream, B, (int)N, nblk, r, tol_r, params, rot,
                                        (const int*)state, tab);
-                else if (R <= 512)
-                    hipLaunchKernelGGL((k_jacobi_reg<8, 1>), dim3(grid), dim3(512), 0, h->stream, B, (int)N, nblk, r, tol_r, params, rot,
-                                       (const int*)state, tab);
-                else if (!one)
-                    hipLaunchKernelGGL((k_jacobi_reg<8, 2>), dim3(grid), dim3(512), 0, h->stream, B, (int)N, nblk, r, tol_r, params, rot,
-                                       (const int*)state, tab);
                 else
-                    hipLaunchKernelGGL((k_jacobi_reg<16, 1>), dim3(grid), dim3(1024), 0, h->stream, B, (int)N, nblk, r, tol_r, params, rot,
+                    hipLaunchKernelGGL((k_jacobi_reg<8, 2>), dim3(grid), dim3(512), 0, h->stream, B, (int)N, nblk, r, tol_r, params, rot,
                                        (const int*)state, tab);
             }
             hipLaunchKernelGGL(k_jr_sweep_end, dim3(1), dim3(1), 0, h->stream, rot, state);
@@ -1409,7 +1401,7 @@ int jacobi_factor_f64(Handle* h, double* B, int64_t N, double* V, double* sig_de
                            floor_rel * floor_rel);
         TLSQ_HIP(h, hipGetLastError());
         const double tol_r = std::max(2.0 * eps * sqrt((double)N), 4.0 * eps);
-        if (N >= 64 && N <= 1024 && !dev_is(DEV_NO_JACOBI_REG, '1')) {
+        if (N >= 64 && N <= 1024) {
             // register-resident block pairs (k_jacobi_reg): blocks of 16 columns, nblk - 1 launches per sweep
             int* state = reinterpret_cast<int*>(reinterpret_cast<char*>(scal) + 160);
             TLSQ_TRY(jr_run_sweeps(h, B, N, tol_r, params, rot, state, nullptr, nullptr, nullptr, 0, 40, &sweep, &converged));

@@ -546,12 +546,10 @@ int matfun_sign_batched(Handle* h, const double* K, const double* K2, int64_t N,
     };
     double l = std::min(std::max(l0, 1e-12), 0.5), u = 1.0;
     const double ga = 3.4445, gb = -4.7750, gc = 2.0315;
-    const bool minimax_all = dev_is(DEV_SLICE_SCHED, 'm');
-    if (!minimax_all)
-        while (l < 0.60 && it < 40) {   // (the growth quintic takes [0.22, 1.2] into [0.68, 1.2]: its own minimum near x = 1.05)
-            TLSQ_TRY(quintic_step(ga, gb, gc));
-            image(ga, gb, gc, l, u);
-        }
+    while (l < 0.60 && it < 40) {   // (the growth quintic takes [0.22, 1.2] into [0.68, 1.2]: its own minimum near x = 1.05)
+        TLSQ_TRY(quintic_step(ga, gb, gc));
+        image(ga, gb, gc, l, u);
+    }
     for (int s = 0; s < 24 && it < 60; ++s) {
         if (std::max(1.0 - l, u - 1.0) < 1e-6) break;
         OddQuintic p;
@@ -752,10 +750,8 @@ static int mf_mul(Handle* h, const double* A, const double* B, double* C, int64_
 }
 // C = A B in full (no symmetry assumed): C[i, j] = sum_k A[i, k] B[k, j], all three column-major.  The coupled iteration below
 // is stable as written (Higham, Functions of Matrices, sec. 6.4); mirroring one triangle of Y T and T Z would replace its
-// small commutator errors by errors of the same size in the iterates themselves (TLSQ_MATFUN_SYM=1: the symmetric form).
+// small commutator errors by errors of the same size in the iterates themselves.
 static int mf_mul_full(Handle* h, const double* A, const double* B, double* C, int64_t N) {
-    const bool sym = dev_is(DEV_MATFUN_SYM, '1');
-    if (sym) return mf_mul(h, A, B, C, N);
     // gemm convention: Cm[j + i ldc] = sum_k Aop(i, k) Bop(k, j); with Aop(i, k) = B[k + i ld] (B's column i) and
     // Bop(k, j) = A[j + k ld] (A's row j):  Cm[j + i ld] = sum_k A[j, k] B[k, i] = (A B)[j, i]
     return gemm_f64(h, true, false, B, N, A, N, C, N, N, N, N, false);
@@ -873,7 +869,7 @@ int matfun_invsqrt(Handle* h, const double* B, int64_t N, double hi, double* Z, 
     double st[3];
     // (k_small_mm, full results: three launches per step - the element-wise step rides in the first product's epilogue and the
     //  iterates change buffers instead of being copied back - against nine through the tiled GEMM)
-    const bool small = N <= 2048 && !dev_is(DEV_NO_SMALL_MM, '1') && !dev_is(DEV_MATFUN_SYM, '1');
+    const bool small = N <= 2048 && !dev_is(DEV_NO_SMALL_MM, '1');
     double *Zc = Z, *Yc = Y, *Wc = W;   // current Z, current Y, the free buffer
     int it = 0;
     int first_test = 3;

@@ -36,12 +36,7 @@ const char* dev_get(DevKey k) { return g_dev_set[k] ? g_dev_val[k].c_str() : nul
 int dev_set(const char* name, const char* value) {
     if (!name) return TLSQ_ERR_ARG;
     if (strncmp(name, "TLSQ_", 5) == 0) name += 5;
-#ifdef TLSQ_DEV_SWITCHES
-    const int nkeys = DEV_COUNT;
-#else
-    const int nkeys = DEV_LIVE_COUNT;   // (the ablation switches exist in development builds only: common.hpp)
-#endif
-    for (int k = 0; k < nkeys; ++k)
+    for (int k = 0; k < DEV_COUNT; ++k)
         if (strcmp(name, kDevNames[k]) == 0) {
             g_dev_set[k] = value != nullptr;
             g_dev_val[k] = value ? value : "";
@@ -67,18 +62,6 @@ void host_trace_dump() {
         fprintf(stderr, " %s %+.1f us |", g_host_marks[i].tag, i ? (g_host_marks[i].t - g_host_marks[i - 1].t) * 1e3 : 0.0);
     fprintf(stderr, " total %.1f us\n", (g_host_marks[g_host_nmarks - 1].t - g_host_marks[0].t) * 1e3);
     g_host_nmarks = 0;
-}
-
-void dev_load_env() {
-#ifdef TLSQ_DEV_SWITCHES
-    static bool done = false;
-    if (done) return;
-    done = true;
-    for (int k = 0; k < DEV_COUNT; ++k) {
-        const std::string var = std::string("TLSQ_") + kDevNames[k];
-        if (const char* e = getenv(var.c_str())) (void)dev_set(kDevNames[k], e);
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -495,10 +478,9 @@ int second_stream(Handle* h) {
     if (h->stream_b) return TLSQ_OK;
     // (highest priority: its workgroups are few and large - they should get a CU as soon as one has room)
     int least = 0, greatest = 0;
-    const bool no_prio = dev_is(DEV_OVERLAP_NOPRIO, '1');
     const char* cp = dev_get(DEV_CERT_PRIO);   // (experiment: "low" / "normal" instead of the highest priority)
     const bool want_low = cp && cp[0] == 'l', want_normal = cp && cp[0] == 'n';
-    if (!no_prio && !want_normal && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least &&
+    if (!want_normal && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least &&
         hipStreamCreateWithPriority(&h->stream_b, hipStreamNonBlocking, want_low ? least : greatest) != hipSuccess) {
         (void)hipGetLastError();
         h->stream_b = nullptr;
@@ -560,7 +542,6 @@ int tlsq_create(int device_id, tlsq_handle* out) {
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return TLSQ_ERR_HIP;  // no GPU: fail loudly
-    dev_load_env();
     if (device_id < 0 || device_id >= ndev) return TLSQ_ERR_ARG;
     if (hipSetDevice(device_id) != hipSuccess) return TLSQ_ERR_HIP;
     tlsq_handle h = new (std::nothrow) tlsq_handle_s();

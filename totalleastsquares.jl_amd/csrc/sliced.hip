@@ -234,8 +234,8 @@ int slice_spectrum(Handle* h, int64_t N, const SliceBufs& b, double lam_hi, int 
     const bool dbg = dev_get(DEV_DEBUG) != nullptr;
     const int64_t nn = N * N;
     const int target = [&] { const char* e = dev_get(DEV_SLICE_TARGET); const int v = e ? atoi(e) : 0; return v >= 16 ? std::min(v, maxk) : want; }();
-    const int maxlev = [] { const char* e = dev_get(DEV_SLICE_LEVELS); const int v = e ? atoi(e) : 6; return v >= 1 && v <= 8 ? v : 6; }();
-    const double l0 = [] { const char* e = dev_get(DEV_SLICE_L0); const double v = e ? atof(e) : 1e-4; return v > 0.0 && v < 0.5 ? v : 1e-4; }();
+    constexpr int maxlev = 6;
+    constexpr double l0 = 1e-4;
     double *K = b.K, *K2 = b.K2, *X = b.X, *W1 = b.W1, *W2 = b.W2, *PJ = b.PJ;
     TLSQ_TRY(small_mm_batched(h, K, nn, K, nn, K2, nn, N, 1, 1.0, 0.0, true, nullptr, 0, 0.0));
     double st3[3], st3b[3];

@@ -29,8 +29,7 @@ int sigma_max_of_gram(Handle* h, const double* G, int64_t N, double rel_tol, dou
     // Five squarings G -> G^32 (MFMA, each rescaled to unit Frobenius norm) concentrate any column on the dominant
     // cluster; started from the dominant column, the Krylov space is that of a ~16-dimensional problem.
     const double* v0 = nullptr;
-    const bool no_pow_start = dev_is(DEV_NO_POWER_START, '1');
-    if (stop_above_sigma == 0.0 && rel_tol <= 1e-9 && N >= 64 && N <= 1024 && !no_pow_start) {
+    if (stop_above_sigma == 0.0 && rel_tol <= 1e-9 && N >= 64 && N <= 1024) {
         void *P1, *P2, *part, *vst;
         TLSQ_TRY(ws_get(h, WS_CP1, (size_t)N * N * 8, &P1));
         TLSQ_TRY(ws_get(h, WS_CP2, (size_t)N * N * 8, &P2));
@@ -40,10 +39,9 @@ int sigma_max_of_gram(Handle* h, const double* G, int64_t N, double rel_tol, dou
         bool quick = false;
         // (N a multiple of 128: one scaling by the trace and five slab-free products, 8 us each at N = 512, instead of five
         //  split-K products + slab reductions + rescalings, 26 us each)
-        // (round 5, measured: eight squarings - G^256, POWER_LEVELS=8 - change nothing at C2: the 15 Lanczos steps that remain
-        //  are the dimension of the dominant cluster of a rank-16 D, not the distance of the start vector from it)
-        const int plev = [] { const char* e = dev_get(DEV_POWER_LEVELS); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 10 ? v : 5; }();
-        TLSQ_TRY(matfun_power_start(h, G, N, (double*)P1, (double*)P2, plev, &src, &quick));
+        // (round 5, measured: eight squarings - G^256 - change nothing at C2: the 15 Lanczos steps that remain are the dimension
+        //  of the dominant cluster of a rank-16 D, not the distance of the start vector from it)
+        TLSQ_TRY(matfun_power_start(h, G, N, (double*)P1, (double*)P2, 5, &src, &quick));
         if (!quick) {
             double* dst = (double*)P1;
             for (int k = 0; k < 5; ++k) {
@@ -119,12 +117,6 @@ static int opnorm_power(Handle* h, const T* Z, int64_t M, int64_t N, int64_t ld,
 
 
 // full eigen-decomposition of G by the block Jacobi solver: V in WS_V
-// does the full solver go through the Cholesky factor (zero columns for numerically-zero eigenvalues)?
-static bool chol_route(int64_t N) {
-    const bool no_chol = dev_is(DEV_NO_CHOL, '1');
-    return N > 64 && !no_chol;
-}
-
 int eig_full(Handle* h, const double* G, int64_t N, double** V_out, SmallSvd& s, int64_t* sweeps, bool allow_warm, int vslot,
              bool need_all_vectors, double lam_hi, int n_out, double val_out, double bulk_hi) {
     void *B, *V, *lam;
@@ -134,7 +126,7 @@ int eig_full(Handle* h, const double* G, int64_t N, double** V_out, SmallSvd& s,
     int64_t sw = 0;
     const bool dbg = dev_get(DEV_DEBUG) != nullptr;
     s.sigma.resize((size_t)N);
-    if (chol_route(N) && !need_all_vectors) {
+    if (N > 64 && !need_all_vectors) {
         // Cholesky-preconditioned route: Jacobi on L = chol(G + delta I); far fewer sweeps on graded spectra and
         // no eigenvector accumulation.  Vectors of numerically-zero eigenvalues come back as zero columns, which
         // is fine for the ALM loop (only sigma_i >= 1/mu are used).
@@ -269,10 +261,7 @@ static int rebuild_factors(Handle* h, const T* Z, int64_t M, int64_t N, int64_t 
     TLSQ_TRY(ws_get(h, slot == 1 ? WS_T2 : slot == 3 ? WS_T3 : WS_T, (size_t)M * r * 8, &T1));   // (3: scratch of the deflated certificate)
     TLSQ_TRY(ws_get(h, WS_AUX0, (size_t)r * 16, &aux));
     // T (M x r, fp64) = Z * Vg
-    const bool no_tsmm = dev_is(DEV_NO_TSMM, '1');
-    const int64_t tsmm_max = [] { const char* e = dev_get(DEV_TSMM_MAXR); return (int64_t)(e ? atoi(e) : 96); }();
-    const bool no_sel = dev_is(DEV_NO_TSMM_SEL, '1');
-    if (r <= 32 && r <= tsmm_max && !no_tsmm && !no_sel) {
+    if (r <= 32) {
         // short lists: selection and weights travel as kernel arguments, V[:, sel] diag(g) is gathered straight into the
         // packed operand of the factor product (no Vg panel, one launch less), Vs on the way
         SelWeights sw;
@@ -286,7 +275,7 @@ static int rebuild_factors(Handle* h, const T* Z, int64_t M, int64_t N, int64_t 
         return TLSQ_OK;
     }
     TLSQ_TRY(gather_scale_host(h, V, N, sel, g, aux, (double*)Vg, (double*)Vs));
-    if (r <= tsmm_max && r <= 96 && !no_tsmm) {
+    if (r <= 96) {
         TLSQ_TRY(tsmm_mixed(h, Z, Prec<T>::f32, ldZ, (const double*)Vg, N, (double*)T1, M, M, N, r));
     } else {
         TLSQ_TRY(gemm_mixed(h, true, false, Vg, 0, N, Z, Prec<T>::f32, ldZ, T1, 0, M, r, M, N, false));
@@ -304,8 +293,7 @@ static int rebuild_from_factors(Handle* h, const double* Tm, const double* Vs, i
         TLSQ_HIP(h, hipMemset2DAsync(Aout, (size_t)ldA * sizeof(T), 0, (size_t)M * sizeof(T), (size_t)N, h->stream));
         return TLSQ_OK;
     }
-    const bool no_store = dev_is(DEV_NO_REBUILD_STORE, '1');
-    if (!no_store && rebuild_store_ok<T>(Aout, M, N, ldA, r)) return launch_rebuild_store<T>(h, Tm, Vs, Aout, M, N, r);
+    if (rebuild_store_ok<T>(Aout, M, N, ldA, r)) return launch_rebuild_store<T>(h, Tm, Vs, Aout, M, N, r);
     TLSQ_TRY(gemm_mixed(h, false, false, Vs, 0, N, Tm, 0, M, Aout, Prec<T>::f32, ldA, N, M, r, false));
     return TLSQ_OK;
 }
@@ -404,7 +392,7 @@ __global__ __launch_bounds__(256) void k_gs_correction(const double* __restrict_
 template <typename T>
 static int polish_derived_vectors(Handle* h, T* U, int64_t M, int64_t d, const std::vector<double>& sig_desc, int64_t m_global,
                                   bool replicated = false) {
-    if (d <= 0 || M <= 0 || dev_is(DEV_NO_U_POLISH, '1')) return TLSQ_OK;
+    if (d <= 0 || M <= 0) return TLSQ_OK;
     // replicated: the panel is the same on every rank of a group (the N x N right vectors), not a row shard: no collectives
     struct CommOff {
         Handle* h;
@@ -540,15 +528,13 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
         if (st_alloc < 0) return st_alloc;
     }
     T *Y = (T*)Yv, *R = (T*)Rv;
-    const bool no_fuse = dev_is(DEV_NO_FUSED_SWEEP, '1');
     const bool no_zsweep = dev_is(DEV_NO_ZSWEEP, '1');
-    const bool no_first = dev_is(DEV_NO_FIRST_SHRINK, '1');
     // The E-free loop (sweeps.hip, k_zsweep): E is not kept while the loop runs - Z is updated in place, Y is double-buffered
     // (the caller's E panel is the second buffer) and the factors of the previous A are kept, from which the returned E is
     // formed once after the loop.  Every plain call runs this way; the `hankel` flag (A is modified after the rebuild) and
     // the svd / opnorm hooks keep the classic sweeps with their E and Z double buffers.
     // (the GPU form of the randomized hook only changes where V and the singular values come from: it runs E-free as well)
-    const bool zmode = !no_zsweep && !no_fuse && !no_first && !ro.hankel && ro.iters >= 1 &&
+    const bool zmode = !no_zsweep && !ro.hankel && ro.iters >= 1 &&
                        !(opts && ((opts->svd_mode != TLSQ_SVD_FULL && opts->svd_mode != TLSQ_SVD_RANDOMIZED) ||
                                   opts->opnorm_mode != TLSQ_OPNORM_EXACT));
     // ResolvedOpts::factors_out: the caller may pass A == nullptr; the panel is allocated the first time something needs it
@@ -573,7 +559,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     // "not certified": Z is double-buffered like Y (the sweep writes Z_{k+1} to the other buffer) and so is the Gram matrix
     // (the Gram of Z_{k+1} goes to the other slot); a failed certificate throws the queued work away and serves iteration k
     // again through the retries / the TSQR route (FAIL_CERT_AT=k injects one for the tests).
-    const bool spec = zmode && !dev_is(DEV_NO_CERT_ASYNC, '1') && !dev_is(DEV_NO_CERT_OVERLAP, '1') && N <= kFullEigMaxN &&
+    const bool spec = zmode && !dev_is(DEV_NO_CERT_ASYNC, '1') && N <= kFullEigMaxN &&
                       (size_t)n * sizeof(T) <= ((size_t)1 << 31) && h->mailbox && h->mailbox_bytes >= 32768 &&
                       !dev_is(DEV_NO_MAILBOX, '1') &&
                       // (lowrankfilter on an implicit Hankel panel promises four resident panels: a fifth only while it is small)
@@ -591,9 +577,8 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     const int Gslot[2] = {WS_G, spec ? WS_G3 : WS_G};
     int gcur = 0;                // the Gram matrix of the current Z sits in (or is computed into) workspace slot Gslot[gcur]
     // ... and the factor product of the rebuild is queued behind the Rayleigh-Ritz finish with a device-side selection list
-    const bool spec_rebuild = zmode && !dev_is(DEV_NO_SPEC_REBUILD, '1') && !dev_is(DEV_NO_TSMM, '1') && !dev_is(DEV_NO_TSMM_SEL, '1') &&
-                              !dev_is(DEV_NO_TSMM_SELV, '1') && !dev_is(DEV_NO_MAILBOX, '1') && (N & 3) == 0 && N <= kFullEigMaxN &&
-                              ro.maxrank >= 32;
+    const bool spec_rebuild = zmode && !dev_is(DEV_NO_SPEC_REBUILD, '1') && !dev_is(DEV_NO_MAILBOX, '1') && (N & 3) == 0 &&
+                              N <= kFullEigMaxN && ro.maxrank >= 32;
     int64_t n_spec_hits = 0;
     const int64_t fail_cert_at = [] { const char* e = dev_get(DEV_FAIL_CERT_AT); return (int64_t)(e ? atoll(e) : 0); }();
     T* Ybuf[2] = {Y, E};         // E-free loop: Y_k sits in Ybuf[ycur], the sweep writes Y_{k+1} to the other one
@@ -604,8 +589,6 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     double mu_iter = 0.0;        // mu of the last iteration that ran
     int cur = 0;                 // index of the buffers holding E_k, Z_k
     bool have_next = false;      // E_k, Z_k already produced by the previous iteration's fused sweep
-    const bool no_fuse_rebuild = dev_is(DEV_NO_FUSED_REBUILD, '1');
-    const bool no_cert_overlap = dev_is(DEV_NO_CERT_OVERLAP, '1');
     const double *Tm_last = nullptr, *Vs_last = nullptr;   // factors of the last A (see fuse_rebuild below)
     int64_t r_last = 0;
     bool a_pending = false;                                // the last A exists only as Tm_last * Vs_last'
@@ -813,10 +796,8 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     // 65536 x 4096).  opnorm(residual), in the few iterations whose cost bound does not settle the test, still goes through the
     // Gram matrix of R (Lanczos on the operator R'R needs ~100 steps of two panel passes: 46 ms).  Iteration 1 is the reference's
     // full svd: the certified subspace solver on the Gram matrix.  Default for fp32 panels, whose operator products run on the
-    // fp32 MFMA (op_gram_f32); fp64 panels keep the Gram matrix below N = 8192 (their skinny products are not faster than it)
-    // unless HOOK_SKETCH=1.
-    const bool hook_sketch = opts && opts->svd_mode == TLSQ_SVD_RANDOMIZED && N > kFullEigMaxN &&
-                             (Prec<T>::f32 ? !dev_is(DEV_HOOK_SKETCH, '0') : dev_is(DEV_HOOK_SKETCH, '1'));
+    // fp32 MFMA (op_gram_f32); fp64 panels keep the Gram matrix below N = 8192 (their skinny products are not faster than it).
+    const bool hook_sketch = opts && opts->svd_mode == TLSQ_SVD_RANDOMIZED && N > kFullEigMaxN && Prec<T>::f32;
     auto panel_op = [&](const T* P) {
         GramOp o;
         o.Z = P;
@@ -831,7 +812,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     // (large fp32 panels: the fp16-split Gram matrix of the set-up needs max |D| for its scale BEFORE it runs - the pass stays in
     //  line there and its result doubles as that scale, see below)
     const bool maxabs_async = !(ro.hankel_lazy && ro.hankel_y) && !cb_opnorm && !hook_opnorm && !implicit_gram && !h->comm &&
-                              !(Prec<T>::f32 && N > kFullEigMaxN) && !dev_is(DEV_NO_MAXABS_ASYNC, '1');
+                              !(Prec<T>::f32 && N > kFullEigMaxN);
     if (ro.hankel_lazy && ro.hankel_y) {   // every sample of the window appears in its Hankel matrix (lag <= L): max |H| = max |y|
         const HankelGeom& hg = ro.hankel_geom;
         const int64_t Nw = (ro.hankel_K - 1) * hg.lag + N / hg.Dch;
@@ -887,10 +868,6 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     const double d_norm = norm2;                                   // :180
     // :181 Y = D / dual_norm is folded into the first shrink (launch_first_shrink, one pass over D instead of three)
     bool y_pending = true;
-    if (no_first) {
-        TLSQ_TRY(launch_div_scalar<T>(h, D, Y, n, (T)dual_norm));      // :181
-        y_pending = false;
-    }
     double mu = 1.25 / norm2;                                      // :182
     const double mubar = mu * 1.0e7;                               // :183
     int64_t sv = 10, svp = 10;                                     // :184
@@ -902,10 +879,10 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     SmallSvd s;
     double* V = nullptr;
     // warm-started subspace iteration (falls back to the full Jacobi solver whenever it cannot certify the
-    // count).  TLSQ_FULL_EIG=1 forces the full solver every iteration.
+    // count).
     SubspaceState sub;
     int64_t hook_cols = 0;   // columns of the block buffer (WS_SX) holding the last decomposition's sorted Ritz vectors: the hook's warm start
-    if (N > kFullEigMaxN && !dev_is(DEV_COLD_GROW, '0')) sub.cold_p = 34;   // (large mode: see the block growth below)
+    if (N > kFullEigMaxN) sub.cold_p = 34;   // (large mode: see the block growth below)
     // (the hook's Rayleigh-Ritz product Z Q and eigenvector matrix of this iteration, when they are still on the device: the
     //  factor of the rebuild is taken from them - SubspaceState::hook_zq)
     const float* hook_zq = nullptr;
@@ -913,13 +890,12 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     const double* hook_S = nullptr;
     std::vector<int32_t> hook_order;
     const int64_t pmax = subspace_max_block(N);
-    const char* force_full = dev_get(DEV_FULL_EIG);
     // Large mode (N > 2048): the full Jacobi solvers do not apply (their column blocks live in LDS); every SVD step
     // has to be served by the certified subspace iteration, whose block is enlarged on demand.  Ranks beyond
     // the largest block (subspace_max_block) are reported as TLSQ_ERR_UNSUPPORTED, and the two-level refinement
     // of very late iterations is not available.
     const bool large = N > kFullEigMaxN;
-    const bool use_subspace = large || (!hook_svd && !(force_full && force_full[0] == '1') && pmax >= 11 && N >= 24);
+    const bool use_subspace = large || (!hook_svd && pmax >= 11 && N >= 24);
     bool v_is_full = false;
     double sigma_top_prev = 0.0;
     int64_t n_rroute = 0;   // iterations whose SVD step was served by the TSQR route
@@ -928,8 +904,6 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     // subspace solver cannot certify a count there, so it is not even tried until a dense result shows a gap again
     bool bulk_tail = false;
     bool power_vec_valid = false;   // the power-iteration vector of the cost evaluation has been started in this call
-    const bool no_power_lb = dev_is(DEV_NO_POWER_LB, '1');
-    const bool no_gram_dense = dev_is(DEV_NO_GRAM_DENSE, '1');
     // HBM traffic the panel-sized kernels of this call have to move (algorithmic bytes of what was launched: panel
     // passes x M x N x sizeof(T)); reported in tlsq_rpca_info
     const double panel_bytes = (double)n * sizeof(T);
@@ -1000,8 +974,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     // whose rounding is relative to ||Z2||^2 ~ (1/mu)^2 instead of sigma_max(Z)^2.  Courant-Fischer: sigma_{|S|+1}(Z) <=
     // sigma_max(Z (I - X_S X_S')) < 1/mu, and Cauchy interlacing puts |S| singular values above 1/mu - the count is |S|.
     // The Ritz values outside S (pad columns: noise of G) are zeroed so that nobody counts them.
-    const bool no_defl = dev_is(DEV_NO_DEFLATED_CERT, '1');
-    const bool defl_possible = !no_defl && use_subspace && !large && !hook_svd && !implicit_gram && !Prec<T>::f32;
+    const bool defl_possible = use_subspace && !large && !hook_svd && !implicit_gram && !Prec<T>::f32;
     auto deflated_certificate = [&](const T* Zp, const double* X, SmallSvd& sv_, double inv_mu_, bool* pass) -> int {
         *pass = false;
         const double tau2 = inv_mu_ * inv_mu_;
@@ -1055,9 +1028,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     // by Newton-Schulz iterations (matfun.hip: ~100 N x N x N MFMA products, 2-3 ms) and one M x N x N product.  A sign
     // iteration that does not converge (an eigenvalue within ~1e-10 of the threshold) or a trace that is not an integer to
     // 1e-6 leaves the iteration to the TSQR route.  A_k has no factor form afterwards: see last_no_factors.
-    const bool no_matfun = dev_is(DEV_NO_MATFUN_ROUTE, '1');
-    const bool matfun_possible = !no_matfun && use_subspace && !large && !hook_svd && !implicit_gram && !Prec<T>::f32 &&
-                                 N >= 64 && N <= 1024;
+    const bool matfun_possible = use_subspace && !large && !hook_svd && !implicit_gram && !Prec<T>::f32 && N >= 64 && N <= 1024;
     bool last_no_factors = false, prev_no_factors = false;   // A_k / A_{k-1} exist only as panels (E-free loop: how E is formed)
     int64_t mf_rS_prev = -1;   // size of the deflated set of the last matrix-function iteration (-1: none yet)
     int64_t mf_k2_last = 0;    // how many values below the dominant set it counted above the threshold
@@ -1094,7 +1065,6 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
         // pairs that no block holds: 3 of 35 iterations and half of the run time at 20000 x 512 with noise 1e-2 (110 -> 65
         // ms).  1e7 fails the residual test; 1e5 from the start costs clean data a digit (A to 5e-11 instead of 1e-11).
         const double dfl_env = [] { const char* e = dev_get(DEV_MATFUN_DEFL); const double v = e ? atof(e) : 0.0; return v > 1.0 ? v : 0.0; }();
-        const double cond_base = [] { const char* e = dev_get(DEV_MATFUN_COND); const double v = e ? atof(e) : 0.0; return v > 1.0 ? v : 1e4; }();
         std::vector<int32_t> sel;
         std::vector<double> gw;
         double stop = 0.0;
@@ -1133,7 +1103,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
             // What stays in G2 has to be (a) small enough for G2's own rounding to sit far below the threshold and (b) within
             // 10 x the level of the threshold: the inverse square root loses eps * cond(B) of its relative accuracy.
             const double next = cnt < ss.ncols ? ss.sigma[ss.order[cnt]] : 0.0;
-            const double cond_max = cond_base * (dfl / 1e3);
+            const double cond_max = 1e4 * (dfl / 1e3);
             if (!(noise_rel * next * next < 1e-4 * tau2) || !(next * next <= cond_max * tau2)) {
                 if (dbg) fprintf(stderr, "  matrix-function route: declined at %.0e / mu^2 (next^2 mu^2 = %.2e, noise %.2e)\n", dfl, next * next / tau2, noise_rel * next * next / tau2);
                 continue;
@@ -1368,12 +1338,12 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
                 g[p] = ro.nukeA ? (sg - inv_mu) / sg : 1.0;            // :205-213
             }
             mu_next = std::min(mu * ro.rho, mubar);                    // :223
-            fuse = !no_fuse && k < ro.iters;
+            fuse = k < ro.iters;
             // large panels: A = T Vs' is not written at all, the fused sweep below forms it in registers from the
             // factors (7 panel passes per iteration instead of 8 + the pass of the skinny GEMM that writes A)
             if (zmode) fuse_rebuild = fuse && svp <= 32;   // (A in registers; above 32 columns it is stored and read back)
             else
-                fuse_rebuild = fuse && !no_fuse_rebuild && !ro.hankel && !hook_opnorm &&
+                fuse_rebuild = fuse && !ro.hankel && !hook_opnorm &&
                                rebuild_update_shrink_ok<T>(D, E, Y, R, Ebuf[cur ^ 1], Zbuf[cur ^ 1], M, N, svp);
             // fp32 panels, ranks 33..80 (BASELINE config 5: 65536 x 4096, rank 64): the factors in fp32 - T32 = Z Vg on the fp32 MFMA
             // (opgram32.hip) - and A_k formed tile by tile on the fp32 MFMA inside the sweep (sweeps.hip, k_zsweep_wide) instead of a
@@ -1392,8 +1362,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
                     TLSQ_TRY(gather_scale_host(h, V, N, sel, g, auxp, (double*)Vgp, (double*)Vsp));
                     int lw = 0;
                     bool from_zq = false;
-                    if (hook_zq && hook_zq == (const float*)h->ws[WS_OPT].p && (int64_t)hook_order.size() == hook_zq_p &&
-                        !dev_is(DEV_NO_HOOK_ZQ, '1')) {
+                    if (hook_zq && hook_zq == (const float*)h->ws[WS_OPT].p && (int64_t)hook_order.size() == hook_zq_p) {
                         // Z X[:, sel] diag(g) = (Z Q) S[:, order[sel]] diag(g): the product Z Q of the hook's Rayleigh-Ritz step is
                         // still in WS_OPT (nothing has run an operator product since) - no pass over the panel
                         std::vector<int32_t> cols((size_t)svp);
@@ -1508,7 +1477,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
             sigma_top = kout > 0 ? cb_sigma(0) : 0.0;
             sigma_top_prev = sigma_top;
             mu_next = std::min(mu * ro.rho, mubar);                    // :223
-            fuse = !no_fuse && k < ro.iters;
+            fuse = k < ro.iters;
             fuse_rebuild = false;
             Tm_last = Vs_last = nullptr;
             r_last = svp;
@@ -1627,7 +1596,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
             sub.fail = SubspaceState::FAIL_CERT;
         } else {
             sub.noise_rel = noise_rel;
-            sub.defer_certificate = !no_cert_overlap;
+            sub.defer_certificate = true;
             sub.cert_async = spec && k < ro.iters;
             if (spec_rebuild && sub.valid && G) {
                 // the buffers rebuild_factors would take for this iteration (the E-free loop keeps two pairs in turn), at full width
@@ -1698,9 +1667,8 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
                 const int64_t cap = std::min<int64_t>(pmax, N);
                 if (grow) {
                     // (large mode doubles: a cold round of a wide block costs a millisecond, and ranks there are rarely below 30 -
-                    //  18 -> 34 -> 51 -> 76 for BASELINE config 5's rank 64 became 34 -> 68; COLD_GROW=0: the old steps)
-                    const bool fast_grow = large && !dev_is(DEV_COLD_GROW, '0');
-                    const int64_t newp = std::min<int64_t>(cap, sub.p + std::max<int64_t>(16, fast_grow ? sub.p : sub.p / 2));
+                    //  18 -> 34 -> 51 -> 76 for BASELINE config 5's rank 64 became 34 -> 68)
+                    const int64_t newp = std::min<int64_t>(cap, sub.p + std::max<int64_t>(16, large ? sub.p : sub.p / 2));
                     if (newp == sub.p && why == SubspaceState::FAIL_SMALL) break;   // the rank exceeds the largest block
                     if (sub.valid && newp > sub.p) {
                         double* X = (double*)h->ws[WS_SX].p;
@@ -1728,7 +1696,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
         if (!hook_now) hook_cols = (fast_ok && sub.valid) ? sub.p : 0;   // (the sorted block the certified solver leaves in WS_SX)
         if (fast_ok) {
             ++sub.fast;
-        } else if (!hook_now && G && !no_gram_dense && (double)ro.m_global > 400.0 * (double)N) {
+        } else if (!hook_now && G && (double)ro.m_global > 400.0 * (double)N) {
             // Very tall panels: the TSQR route would stream the whole panel ~N/16 times, the Gram matrix is already
             // there.  Dense decomposition of G (Jacobi on its Cholesky factor), believed under the same rule as the
             // subspace result: no eigenvalue within the Gram route's uncertainty of the threshold.
@@ -1801,7 +1769,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
                 sigma_top = stop_m;
                 sigma_top_prev = stop_m;
                 mu_next = std::min(mu * ro.rho, mubar);                    // :223
-                fuse = !no_fuse && k < ro.iters;
+                fuse = k < ro.iters;
                 fuse_rebuild = false;
                 Tm_last = Vs_last = nullptr;
                 r_last = svp;
@@ -1876,8 +1844,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
         // by sqrt(N / rank): the E-free sweep keeps the maximum on the side (one slot per rank: the sum all-reduce of row
         // shards then carries every rank's maximum unchanged), and "not converged" is settled without the Gram of R in all
         // iterations but the last one or two.
-        const bool no_maxb = dev_is(DEV_NO_MAX_BOUND, '1');
-        const int maxslot = (zmode && sumsq_dev && !no_maxb && h->nranks <= 8) ? h->rank : -1;
+        const int maxslot = (zmode && sumsq_dev && h->nranks <= 8) ? h->rank : -1;
         // The residual panel R_k is only read by the cost evaluation.  While the Frobenius bound of the previous
         // iteration was far above tol this one's will be too (the cost shrinks by ~rho per iteration): the sweep then
         // does not store R_k at all (one panel pass less); should the bound disagree, R_k is recomputed below.
@@ -1894,8 +1861,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
         // (not when the previous iteration's cost bound - tight since it is the largest entry of the residual - was already
         //  within 1.6 tol: this iteration is then most likely the last one, and a Gram queued now would be the wasted one;
         //  should the loop go on after all, the Gram is computed at the top of the next iteration instead)
-        const double last_guess = [] { const char* e = dev_get(DEV_LAST_GUESS); return e ? atof(e) : 1.6; }();
-        const bool likely_last = maxslot >= 0 && prev_lower > 0.0 && prev_lower < last_guess * ro.tol;   // (infinity before the first bound: false)
+        const bool likely_last = maxslot >= 0 && prev_lower > 0.0 && prev_lower < 1.6 * ro.tol;   // (infinity before the first bound: false)
         const bool gram_next = sumsq_dev && !r_next && !implicit_gram && !likely_last && !hook_sketch;
         bool gram_queued = false;
         bool fused_gram = false;   // the sweep kernel has accumulated the Gram of Z_{k+1} as well (fused.hip): only its slabs are left to add
@@ -1908,7 +1874,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
             if (!fuse_rebuild) hy_sweep = nullptr;           // A from memory: the linear kernel reads a real D
             if (!hy_sweep) TLSQ_TRY(panel_D(&D));
         }
-        auto sweep_rows = [&](int64_t r0, int64_t r1, size_t pad_lds) -> int {
+        auto sweep_rows = [&](int64_t r0, int64_t r1) -> int {
             if (zmode)
                 return launch_zsweep<T>(h, D, Tm_last, Vs_last, fuse_rebuild ? (T*)nullptr : A, Ybuf[ycur], Ybuf[ycur ^ 1],
                                         Zbuf[zc], Rst, M, N, svp, (T)mu, (T)inv_mu, ro.nonnegA ? 1 : 0, (T)(1.0 / mu_next),
@@ -1917,7 +1883,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
             return launch_rebuild_update_shrink<T>(h, D, Tm_last, Vs_last, E, Y, Rst, Ebuf[cur ^ 1], Zbuf[cur ^ 1], M, N, svp,
                                                    (T)mu, ro.nonnegA ? 1 : 0, (T)(1.0 / mu_next), (T)(lam / mu_next),
                                                    ro.nonnegE ? 1 : 0, sumsq_dev, sumsq_next, (const T*)ro.hankel_y,
-                                                   ro.hankel_K, r0, r1, pad_lds, ro.hankel_geom);
+                                                   ro.hankel_K, r0, r1, ro.hankel_geom);
         };
         // (a max |Z| left by the previous sweep - Handle::absmax_panel - described the Z_k of this iteration's SVD step: whatever
         //  needed it has been queued, and the panel is about to be rewritten)
@@ -1952,7 +1918,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
             hbm_sweeps += (Rst ? 6.0 : 5.0) * panel_bytes;
         } else if (zmode && !fuse_rebuild) {
             // A_k above 32 columns: stored by the rebuild, read back here (6 panel passes + R)
-            TLSQ_TRY(sweep_rows(0, 0, 0));
+            TLSQ_TRY(sweep_rows(0, 0));
             z_swept = true;
             hbm_sweeps += (Rst ? 7.0 : 6.0) * panel_bytes;
         } else if (fuse_rebuild) {
@@ -1961,17 +1927,14 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
             // milliseconds - the sweep goes row chunk by row chunk and the Gram of a finished chunk runs beside the sweep
             // of the next one, on the handle's second stream.  The two kernels do share the CUs, but each runs at about
             // half speed meanwhile (kernel trace at 1e7 x 256, 8 chunks: sweep chunk 2.6 ms alone / 3.7 beside a Gram
-            // chunk, Gram chunk 1.5 / 3.6): 30.9 ms for the pair instead of 35.0, nothing at 200000 x 512 (TLSQ_OVERLAP_CHUNKS
-            // forces a chunk count, 1 = off).
-            const int env_chunks = [] { const char* e = dev_get(DEV_OVERLAP_CHUNKS); return e ? atoi(e) : -1; }();
+            // chunk, Gram chunk 1.5 / 3.6): 30.9 ms for the pair instead of 35.0, nothing at 200000 x 512.
             const bool f32mfma_gram = Prec<T>::f32 && N > 2048;   // (gram_any's choice: that kernel is not chunked)
             int nchunks = (gram_next && !f32mfma_gram && M * N >= ((int64_t)1 << 30)) ? 8 : 1;
-            if (env_chunks >= 1 && env_chunks <= 8 && gram_next && !f32mfma_gram) nchunks = env_chunks;
             // fp64 panels of 256 columns (lowrankfilter's n = 256): sweep and Gram in ONE kernel (fused.hip) - the rows of
             // Z_{k+1} feed the MFMA from LDS on their way to memory, the Gram reads nothing from HBM and needs no second
             // stream.  Its slabs are reduced where the next Gram is queued below.
             if constexpr (std::is_same<T, double>::value) {
-                if (zmode && gram_next && env_chunks < 0 &&
+                if (zmode && gram_next &&
                     fused_zgram_ok(M, N, svp, D, Ybuf[ycur], Ybuf[ycur ^ 1], Zbuf[zc], Zbuf[zc ^ 1], Rst, hy_sweep != nullptr,
                                    lam / mu_next, ro.hankel_geom)) {
                     // The sweep was going to store R_k, i.e. the cost of this iteration will most likely be evaluated (the
@@ -1983,7 +1946,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
                     //  C3 two of four such iterations are still settled by the bounds and would pay for the Gram of Z_{k+1}
                     //  they did not accumulate)
                     //  (N = 256 only: at N = 512 the off-diagonal block would need the stored R_k)
-                    fused_gr = Rst != nullptr && prev_cost_evaluated && N == 256 && group_fused_shape && !dev_is(DEV_NO_FUSED_GR, '1');
+                    fused_gr = Rst != nullptr && prev_cost_evaluated && N == 256 && group_fused_shape;
                     TLSQ_TRY(fused_zgram_plan(h, M, N, &fused_pl));
                     TLSQ_TRY(launch_fused_zgram(h, fused_pl, D, Tm_last, Vs_last, Ybuf[ycur], Ybuf[ycur ^ 1], Zbuf[zc], Zbuf[zc ^ 1],
                                                 Rst, M, N, svp, mu, inv_mu, ro.nonnegA ? 1 : 0, 1.0 / mu_next, lam / mu_next,
@@ -1997,9 +1960,8 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
                 // (swept and accumulated above)
             } else if (nchunks > 1) {
                 TLSQ_TRY(second_stream(h));
-                // (TLSQ_OVERLAP_LDS: unused dynamic LDS per sweep workgroup, caps its residency per CU - measured: 40 KB
-                // no change, 80 KB, i.e. one sweep workgroup per CU, slower)
-                const size_t pad_lds = [] { const char* e = dev_get(DEV_OVERLAP_LDS); return e ? (size_t)atol(e) : (size_t)0; }();
+                // (capping the residency of the sweep workgroups per CU with unused dynamic LDS was measured: 40 KB no change,
+                // 80 KB, i.e. one sweep workgroup per CU, slower)
                 const int64_t rows_c = ((M + nchunks - 1) / nchunks + 511) / 512 * 512;
                 GramPlan pl;
                 TLSQ_TRY(gram_plan(h, Prec<T>::f32, N, rows_c, nchunks, &pl));
@@ -2007,7 +1969,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
                 TLSQ_TRY(ws_get(h, Gslot[gcur ^ 1], (size_t)N * N * 8, &Gv));
                 for (int c = 0; c < nchunks; ++c) {
                     const int64_t r0 = std::min<int64_t>((int64_t)c * rows_c, M), r1 = std::min<int64_t>(r0 + rows_c, M);
-                    if (r1 > r0) TLSQ_TRY(sweep_rows(r0, r1, pad_lds));
+                    if (r1 > r0) TLSQ_TRY(sweep_rows(r0, r1));
                     TLSQ_HIP(h, hipEventRecord(h->ev_b[c], h->stream));
                     TLSQ_HIP(h, hipStreamWaitEvent(h->stream_b, h->ev_b[c], 0));
                     TLSQ_TRY(gram_launch_chunk(h, h->stream_b, pl, (zmode ? Zbuf[zc ^ 1] : Zbuf[cur ^ 1]) + r0, M, r1 - r0, c));
@@ -2016,7 +1978,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
                 TLSQ_HIP(h, hipEventRecord(h->ev_b[8], h->stream_b));
                 gram_queued = true;   // (h->stream waits for ev_b[8] below, behind the publication of the Frobenius sums)
             } else {
-                TLSQ_TRY(sweep_rows(0, 0, 0));
+                TLSQ_TRY(sweep_rows(0, 0));
             }
             if (zmode) z_swept = true;
             hbm_sweeps += (((Rst && !fused_gr) ? 7.0 : 6.0) - (zmode ? 1.0 : 0.0) - (ro.hankel_y ? 1.0 : 0.0)) * panel_bytes;
@@ -2195,7 +2157,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
                 //  within a few per cent of its norm, so "not converged" is not what three power steps are going to say - the last
                 //  iteration of a solve went through them, and a host round trip, for nothing)
                 const bool likely_converged = maxslot >= 0 && prev_lower_from_max && prev_lower < 0.9 * ro.tol;
-                if (stop_sigma > 0.0 && !no_power_lb && !likely_converged) {
+                if (stop_sigma > 0.0 && !likely_converged) {
                     // "not converged" from three power steps on the vector carried over from the previous evaluation
                     // (||G v|| <= lambda_max for unit v): no Lanczos run unless the bound falls short of the mark
                     double lb = 0.0;
@@ -2375,7 +2337,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
         // sigma_min >= 2e-4 s (below that the Gram matrix of Z_P loses the value to rounding: tolerance of the returned S) -
         // anything else goes through the TSQR route as before.
         bool deflated_ok = false;
-        if (!dev_is(DEV_NO_DEFLATED_SVD, '1') && !large && !Prec<T>::f32 && V && V == (const double*)h->ws[WS_SX].p &&
+        if (!large && !Prec<T>::f32 && V && V == (const double*)h->ws[WS_SX].p &&
             s.ncols > 0 && s.ncols < N && mu_iter > 0.0 && N >= 64) {
             const double tau = 1.0 / mu_iter, tau2 = tau * tau;
             const double stop = s.sigma[s.order[0]];

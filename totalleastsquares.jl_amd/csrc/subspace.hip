@@ -619,8 +619,7 @@ __global__ __launch_bounds__(256) void k_symm_mfma(const double* __restrict__ G,
 
 int launch_symm_skinny(Handle* h, const double* G, int64_t ldG, const double* X, double* Y, int64_t N, int64_t p) {
     if (p <= 0) return TLSQ_OK;
-    const bool no_mfma = dev_is(DEV_NO_SYMM_MFMA, '1');
-    if (!no_mfma && (reinterpret_cast<uintptr_t>(X) % 16) == 0) {
+    if ((reinterpret_cast<uintptr_t>(X) % 16) == 0) {
         hipLaunchKernelGGL(k_symm_mfma, dim3((unsigned)((N + 15) / 16), (unsigned)((p + 15) / 16)), dim3(256), 0, h->stream, G,
                            ldG, X, Y, (int)N, (int)p);
         TLSQ_HIP(h, hipGetLastError());
@@ -884,8 +883,7 @@ int launch_project_out(Handle* h, const double* X, int64_t c, double* Yb, int64_
 
 int launch_orth(Handle* h, double* Y, double* tmp, double* W, int64_t N, int64_t p, double* status_dev,
                 bool allow_cholqr, bool* used_cholqr, bool one_pass, int64_t c_start) {
-    const bool no_cholqr = dev_is(DEV_NO_CHOLQR, '1');
-    *used_cholqr = allow_cholqr && p <= 512 && !no_cholqr;
+    *used_cholqr = allow_cholqr && p <= 512;
     // Yb (N x pb) -= Y[:, 0:c0] (Y[:, 0:c0]' Yb), the finished columns taken PROJ_CHUNK at a time: k_panel_sub keeps its
     // slice of the coefficients in LDS (64 bytes per finished column), and c_start callers (null-space completion of the
     // returned vectors, N up to 4608) start far beyond the 512 columns the block orthonormalisation itself ever reaches.
@@ -906,8 +904,7 @@ int launch_orth(Handle* h, double* Y, double* tmp, double* W, int64_t N, int64_t
         // long vectors go block by block: 16 columns are projected twice against the finished ones (two multi-workgroup
         // products per projection) and orthonormalised among themselves by the one-workgroup kernel, whose cost falls
         // with the square of the block width.
-        const bool no_blocked = dev_is(DEV_NO_BLOCKED_CGS2, '1');
-        if (no_blocked || ((N < 2048 || p <= 32) && c_start == 0)) return launch_cgs2(h, Y, N, p, status_dev);
+        if ((N < 2048 || p <= 32) && c_start == 0) return launch_cgs2(h, Y, N, p, status_dev);
         constexpr int64_t GB = 16;
         for (int64_t c0 = c_start; c0 < p; c0 += GB) {
             const int64_t pb = std::min<int64_t>(GB, p - c0);
@@ -1058,7 +1055,7 @@ __device__ __forceinline__ void rs_reduce(double& s0, double& s1, double& m0, do
 
 __global__ __launch_bounds__(256) void k_rr_small(const double* __restrict__ Bg, const double* __restrict__ Hg, int p,
                                                   double* __restrict__ Cout, double* __restrict__ lam_out,
-                                                  double* __restrict__ status, int nt, double tau2, int block_ok) {
+                                                  double* __restrict__ status, int nt, double tau2) {
     // seven 32 x 32 buffers (59 KB): Bh and Hh stay; the others change roles between the factorisation and the refinement
     __shared__ double sBh[RS_P * RS_LD], sH[RS_P * RS_LD], b2[RS_P * RS_LD], b3[RS_P * RS_LD], b4[RS_P * RS_LD];
     __shared__ double b5[RS_P * RS_LD], b6[RS_P * RS_LD];
@@ -1137,7 +1134,7 @@ __global__ __launch_bounds__(256) void k_rr_small(const double* __restrict__ Bg,
         // deviation, L = [I 0; K' L_S], L_S L_S' = S = B_pp - K'K - one p x p x p product and a factorisation of the pad block
         // (4 columns of 20) instead of p dependent column steps.  What the top block really deviates from I is left to the
         // refinement below, which has to remove deviations of that size from C'Hh C anyway.
-        blocked = block_ok && nt >= 1 && nt < p && delta_tt <= 3e-3;
+        blocked = nt >= 1 && nt < p && delta_tt <= 3e-3;
         int k0 = 0;
         if (blocked) {
 #pragma unroll
@@ -1392,7 +1389,7 @@ int launch_rr_small(Handle* h, const double* Y, const double* GY, double* Bm, do
     if (p < 1 || p > RS_P) return set_err(h, TLSQ_ERR_ARG, "rr_small: p = %lld (1 .. %d)", (long long)p, RS_P);
     hipLaunchKernelGGL(k_panel_tn2x, dim3((unsigned)((2 * p * p + 3) / 4)), dim3(256), 0, h->stream, Y, GY, Bm, Hm, (int)N, (int)p);
     hipLaunchKernelGGL(k_rr_small, dim3(1), dim3(256), 0, h->stream, (const double*)Bm, (const double*)Hm, (int)p, Cout, lam,
-                       status, (int)nt, tau2, dev_is(DEV_NO_RR_BLOCKED, '1') ? 0 : 1);
+                       status, (int)nt, tau2);
     TLSQ_HIP(h, hipGetLastError());
     return TLSQ_OK;
 }
@@ -1400,8 +1397,7 @@ int launch_rr_small(Handle* h, const double* Y, const double* GY, double* Bm, do
 int launch_rr_small_only(Handle* h, const double* Bm, const double* Hm, double* Cout, double* lam, double* status, int64_t p,
                          int64_t nt, double tau2) {
     if (p < 1 || p > RS_P) return set_err(h, TLSQ_ERR_ARG, "rr_small: p = %lld (1 .. %d)", (long long)p, RS_P);
-    hipLaunchKernelGGL(k_rr_small, dim3(1), dim3(256), 0, h->stream, Bm, Hm, (int)p, Cout, lam, status, (int)nt, tau2,
-                       dev_is(DEV_NO_RR_BLOCKED, '1') ? 0 : 1);
+    hipLaunchKernelGGL(k_rr_small, dim3(1), dim3(256), 0, h->stream, Bm, Hm, (int)p, Cout, lam, status, (int)nt, tau2);
     TLSQ_HIP(h, hipGetLastError());
     return TLSQ_OK;
 }

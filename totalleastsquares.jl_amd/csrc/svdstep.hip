@@ -23,7 +23,7 @@ static int op_apply(Handle* h, const GramOp& op, int64_t N, const double* X, dou
     if (!op.implicit()) return launch_symm_skinny(h, op.G, N, X, Y, N, p);
     // fp32 panels, blocks of more than 8 columns: both halves on the fp32 MFMA (gemm.hip, op_gram_f32) - the widening kernels
     // below run on the fp64 MFMA at half the rate (narrow blocks, the Lanczos vectors, are bandwidth-bound either way)
-    if (op.z_f32 && op.lowp_ok && p > 8 && !dev_is(DEV_NO_F32_SKINNY, '1')) {
+    if (op.z_f32 && op.lowp_ok && p > 8) {
         for (int64_t c0 = 0; c0 < p; c0 += 96) {
             const int64_t pc = std::min<int64_t>(96, p - c0);
             TLSQ_TRY(op_gram_f32(h, (const float*)op.Z, op.ldZ, op.M, N, X + (size_t)c0 * N, N, Y + (size_t)c0 * N, N, pc));
@@ -207,9 +207,8 @@ int cert_finish(Handle* h, SubspaceState& st, bool* pass) {
     // Still too coarse: the tail is flat and close to the mark (late iterations of a Hankel filter: hundreds of values
     // at 0.7x the threshold).  Three more squarings bring the bound to rank^(1/64) above lambda_max, still rigorous;
     // a Lanczos run (a LOWER bound, hence the 1.5x safety factor) screens first where an N^3 product is not small.
-    const bool no_deep = dev_is(DEV_NO_DEEP_POWERS, '1');
     bool lanczos_done = false;
-    if (st.cert_N > 1024 || no_deep) {
+    if (st.cert_N > 1024) {
         const int lst = lanczos_lmax_f64(h, st.cert_GD, st.cert_N, st.cert_N, 0.02, 48, &lmax, &steps, st.cert_margin);
         if (lst < 0) return lst;
         ++st.n_lanczos_cert;
@@ -220,7 +219,7 @@ int cert_finish(Handle* h, SubspaceState& st, bool* pass) {
             return TLSQ_OK;
         }
         st.cert_tail = lmax;
-        if (lmax >= st.cert_margin || no_deep) return TLSQ_OK;   // an eigenvalue above the mark: the count is wrong
+        if (lmax >= st.cert_margin) return TLSQ_OK;   // an eigenvalue above the mark: the count is wrong
     }
     double c[3] = {0.0, 0.0, 0.0};
     TLSQ_TRY(power_norm_sync(h, st, 5, c, 3));
@@ -333,11 +332,11 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
     double* stat_dev = res_dev + p;
     double* lamH_dev = stat_dev + 8;
     std::vector<double> host((size_t)2 * p + 8);
-    if (hook && !dev_is(DEV_HOOK_CLASSIC, '1')) {
+    if (hook) {
         // The randomized hook as a block power method (round 5).  The reference's hook is `svd(Z, sv)` with a user function of
         // the rsvd kind (src/robustPCA.jl:195-197; test/runtests.jl:388-398 uses rank sv, two power iterations): Q = orth((Z Z')^q Z Omega),
         // then the SVD of Q'Z.  Here on the small side:  X <- orth(G X) `npow` times (2 on the panel operator, 3 on an explicit Gram matrix), then ONE Rayleigh-Ritz step
-        // H = Q'(G Q): three products with the panel pair instead of the five of the two-step form below, one p x p eigenproblem
+        // H = Q'(G Q): three products with the panel pair instead of the five of the two-step form of round 4, one p x p eigenproblem
         // instead of two, and CholeskyQR2 (a handful of multi-workgroup launches) for every orthonormalisation: a block is
         // orthonormalised after EACH product, so its condition number is sigma_1^2 / sigma_p^2 of the panel, not the fourth
         // power a random block has after two products (which needed the column-sequential CGS2: six 0.26 ms one-workgroup
@@ -345,30 +344,25 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
         // the caller says it is still in WS_SX (hook_carry) - Z_k changes little from one ALM iteration to the next, so the
         // block enters already near-invariant - with the last few pad columns refreshed from the hash generator, so that a
         // direction absent from the carried block can still enter; a cold call (iteration 2 after a full decomposition on
-        // another route, HOOK_COLD=1) starts from a random block like the reference's Omega.
+        // another route) starts from a random block like the reference's Omega.
         // A Cholesky factorisation that breaks down (status[1]) repeats the call from a random block with CGS2.
         // (products before the Rayleigh-Ritz step: two on the panel operator - three products in all, the work of rsvd with two power
         //  iterations; three on an explicit Gram matrix, where a product is a 12 us kernel and the extra half power that rsvd's
         //  Q'Z step has over a Rayleigh-Ritz step on G^2 X is cheaper to exceed than to argue about: tools/fuzz_misc.py compares
         //  with the oracle's rsvd to 1e-5)
-        const int npow_default = op.implicit() ? 2 : 3;
-        const int npow = [npow_default] {
-            const char* e = dev_get(DEV_HOOK_POWER);
-            const int v = e ? atoi(e) : npow_default;
-            return v >= 1 && v <= 6 ? v : npow_default;
-        }();
+        const int npow = op.implicit() ? 2 : 3;
         const unsigned int seed32 = (unsigned int)(st.hook_seed * 2654435761ull + 77u);
-        int64_t carry = dev_is(DEV_HOOK_COLD, '1') ? 0 : std::min<int64_t>(st.hook_carry, p);
+        int64_t carry = std::min<int64_t>(st.hook_carry, p);
         // (the last pad columns come from the hash generator at every call, so that a direction absent from the carried block can
-        //  still enter; HOOK_PAD_REFRESH=0 carries all of them - measured: the same seven Jacobi sweeps either way, the Ritz vectors
-        //  inside the dominant cluster rotate by O(1) from one ALM iteration to the next)
-        if (carry > 0 && !dev_is(DEV_HOOK_PAD_REFRESH, '0'))
+        //  still enter; carrying all of them was measured: the same seven Jacobi sweeps either way, the Ritz vectors inside the
+        //  dominant cluster rotate by O(1) from one ALM iteration to the next)
+        if (carry > 0)
             carry = std::max<int64_t>(0, std::min<int64_t>(carry, p - std::max<int64_t>(2, (p - st.hook_rank) / 2)));
         st.hook_carry = 0;
-        double* stat2 = lamH_dev + p;          // 3 status words per intermediate orthonormalisation (npow <= 6)
+        double* stat2 = lamH_dev + p;          // 3 status words per intermediate orthonormalisation (npow <= 3)
         std::vector<double> host2((size_t)3 * 6);
         for (int attempt = 0; attempt < 2; ++attempt) {
-            const bool chol = attempt == 0 && !dev_is(DEV_HOOK_CGS2, '1');
+            const bool chol = attempt == 0;
             if (attempt > 0) carry = 0;
             if (carry < p) TLSQ_TRY(launch_fill_hash(h, (double*)X + (size_t)carry * N, N * (p - carry), seed32 + (unsigned int)attempt));
             double* cur = (double*)Q;
@@ -381,8 +375,8 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
                 bool used = false;
                 // (a carried block consists of Ritz vectors: their images are nearly orthogonal, and the column scaling of the
                 //  second product does not hurt the scaled Cholesky factor - only the last product's block is orthonormalised;
-                //  the refreshed pad columns are projected against the blocks in front of them first, HOOK_ORTH_ALL=1 for every product)
-                const bool skip_orth = chol && carry >= st.hook_rank && t + 1 < npow && !dev_is(DEV_HOOK_ORTH_ALL, '1');
+                //  the refreshed pad columns are projected against the blocks in front of them first)
+                const bool skip_orth = chol && carry >= st.hook_rank && t + 1 < npow;
                 if (skip_orth) {
                     TLSQ_HIP(h, hipMemsetAsync(stat2 + 3 * t, 0, 24, h->stream));
                 } else {
@@ -430,8 +424,8 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
         s.ncols = p;
         sort_desc(s);
         st.hook_zq = nullptr;
-        if (op.implicit() && op.z_f32 && op.lowp_ok && p > 8 && p <= 80 && !dev_is(DEV_NO_F32_SKINNY, '1') &&
-            !dev_is(DEV_OPGRAM_OLD, '1') && op_gram_f32_fast_ok((const float*)op.Z, op.ldZ, op.M, N, p) && op.ldZ == op.M) {
+        if (op.implicit() && op.z_f32 && op.lowp_ok && p > 8 && p <= 80 && !dev_is(DEV_OPGRAM_OLD, '1') &&
+            op_gram_f32_fast_ok((const float*)op.Z, op.ldZ, op.M, N, p) && op.ldZ == op.M) {
             st.hook_zq = (const float*)h->ws[WS_OPT].p;   // (the T32 of the last op_apply: Z Qf, 16 ceil(p / 16) columns)
             st.hook_zq_lw = 16 * (int)((p + 15) / 16);
             st.hook_S = (const double*)S;
@@ -454,7 +448,7 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
         *ok = true;
         return TLSQ_OK;
     }
-    const int max_steps = hook ? 2 : (cold ? 30 : 10) + st.extra_steps;
+    const int max_steps = (cold ? 30 : 10) + st.extra_steps;
     const int64_t ntop = cold ? p : std::min<int64_t>(st.ntop, p);
     int64_t svp = 0;
     bool conv = false;
@@ -463,8 +457,6 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
     bool x_settled = false;   // nothing that writes the block X has been queued since the host read the last step's results
     bool force_cgs2 = cold;   // a random block is far too ill-conditioned for CholeskyQR2
     bool cgs2_sticky = false;
-    const bool no_onepass = dev_is(DEV_NO_ONEPASS, '1');
-    const bool no_rr_fast = dev_is(DEV_NO_RR_FAST, '1');
     const bool dbg = dev_get(DEV_DEBUG) != nullptr;
     // (declined: for the rest of this call the block is not what k_rr_small is made for.  A kernel that keeps declining -
     //  near-degenerate pairs of Ritz values, as a Hankel filter has them - is not tried in the next 2, 4, 8, 16 calls.)
@@ -482,8 +474,8 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
         // multiplication so that they keep tracking the top of the tail spectrum.  Cold (random) start: every
         // column, q = 2 (higher powers would make the random block too ill-conditioned for CGS2).
         // (second and later steps: G X is already there - the Rayleigh-Ritz finish of the previous step formed it with the Ritz
-        //  vectors, GX = (G Q) S - as long as the block has not been re-ordered since: one product less per step, of six in
-        //  a step of the randomized hook, 1.4 ms each at 65536 x 4096)
+        //  vectors, GX = (G Q) S - as long as the block has not been re-ordered since: one product less per step, 1.4 ms each
+        //  at 65536 x 4096)
         if (gx_valid) TLSQ_HIP(h, hipMemcpyAsync(Q, GX, (size_t)N * p * 8, hipMemcpyDeviceToDevice, h->stream));
         else TLSQ_TRY(op_apply(h, op, N, (const double*)X, (double*)Q, p));
         gx_valid = false;
@@ -491,7 +483,7 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
         //  multiplications from then on, and more of them: every column to the power 4 is what the pad columns' condition number
         //  allows, (lambda_pad / lambda_1)^4 ~ 1e-7 at C2; the counted columns alone take 7 and the second step lands under the
         //  residual bound that used to need a third - 100 us of the first ALM iteration.  COLD_TOP=0: as before)
-        const bool cold_top = cold && !hook && step >= 1 && svp >= 1 && svp <= p - 2 && !dev_is(DEV_COLD_TOP, '0');
+        const bool cold_top = cold && step >= 1 && svp >= 1 && svp <= p - 2 && !dev_is(DEV_COLD_TOP, '0');
         const int64_t nt_step = cold_top ? svp : cold ? p : std::min<int64_t>(step == 0 ? ntop : svp, p);   // leading columns treated as wanted
         {
             const int64_t nt = nt_step;
@@ -506,7 +498,6 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
             // pass both orthonormalisations are CholeskyQR2 (~0.3 ms each); a breakdown of the final one repeats the step with
             // CGS2 as before (a breakdown of the intermediate one leaves G X as it is: the final one then decides).
             const bool cold_chol = cold && step == 0 && force_cgs2 && !cgs2_sticky && q == 2 && nt == p && (N > 2048 || p > 32) &&
-                                   !dev_is(DEV_COLD_CGS2, '1') && !dev_is(DEV_NO_CHOLQR, '1') &&
                                    // (the status-guarded finish of the mailbox path leaves X alone when the factorisation breaks down)
                                    h->mailbox && !dev_is(DEV_NO_MAILBOX, '1') && p <= 512 && (size_t)(2 * p + 10) * 8 <= h->mailbox_bytes;
             if (cold_chol) {
@@ -529,9 +520,9 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
         // come from two reductions over the panel and ONE workgroup of p x p products (subspace.hip, k_rr_small) instead of
         // CholeskyQR2, H = Q'GQ and the Jacobi solver; anything that kernel declines (panel too far from orthogonal, a
         // cluster of Ritz values with internal coupling) repeats the step on the classic path.
-        const bool rr_fast = !cold && !force_cgs2 && !rr_fast_declined && !no_rr_fast && p <= 32 && !op.implicit();
+        const bool rr_fast = !cold && !force_cgs2 && !rr_fast_declined && p <= 32 && !op.implicit();
         // one CholeskyQR pass when the previous step on this block cleared the one-pass pivot bound with room to spare
-        const bool one_pass = !cold && !force_cgs2 && !no_onepass && p <= 32 && st.chol_p == p && st.chol_piv >= 0.5;   // (32 = CQ_PMAX: single-block panels)
+        const bool one_pass = !cold && !force_cgs2 && p <= 32 && st.chol_p == p && st.chol_piv >= 0.5;   // (32 = CQ_PMAX: single-block panels)
         if (rr_fast) {
             TLSQ_TRY(op_apply(h, op, N, (const double*)Q, (double*)GQ, p));
             TLSQ_TRY(launch_rr_small(h, (const double*)Q, (const double*)GQ, (double*)H, (double*)HB, (double*)S, lamH_dev, stat_dev, N, p,
@@ -549,7 +540,7 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
         int64_t sw = 0;
         // (the Ritz vectors of a random block's first step only sort the block and count, and the step itself leaves them 1e-3
         //  from their limits: rotations down to 1e-5 instead of 2 eps sqrt(p); COLD_TOL0=0: full accuracy)
-        const double rot_tol0 = cold && !hook && step == 0 && force_cgs2 && p <= 96 && !dev_is(DEV_COLD_TOL0, '0') ? 1e-5 : 0.0;
+        const double rot_tol0 = cold && step == 0 && force_cgs2 && p <= 96 && !dev_is(DEV_COLD_TOL0, '0') ? 1e-5 : 0.0;
         TLSQ_TRY(symeig_f64(h, (const double*)H, p, p, (double*)HB, (double*)S, true, lamH_dev, &sw, true, false, true, rot_tol0));
         dbg_hash(h, "sub.S", S, (size_t)p * p * 8);
         if (sweeps) *sweeps += sw;
@@ -653,8 +644,7 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
         // a cold start is random only once: from the second step on the block consists of Ritz vectors, whose images under
         // G^q are nearly orthogonal again (different norms do not hurt the Cholesky factor) - CholeskyQR2 (18 us instead of 60)
         // unless it has already failed on this block
-        const bool cold_cgs2 = dev_is(DEV_COLD_CGS2, '1');
-        if (cold && !hook && !cgs2_sticky && !cold_cgs2) force_cgs2 = false;   // (the randomized hook keeps its two plain passes)
+        if (cold && !cgs2_sticky) force_cgs2 = false;
         s.sigma.resize((size_t)p);
         double tmax = 0.0;
         bool finite = true;
@@ -710,17 +700,10 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
                 s.sigma[i] = sg_sorted[i];
             }
             std::iota(s.order.begin(), s.order.end(), 0);
-            gx_valid = !dev_is(DEV_NO_GX_REUSE, '1');
+            gx_valid = true;
         }
         svp = 0;
         for (int64_t i = 0; i < p; ++i) svp += (s.sigma[i] >= inv_mu) ? 1 : 0;
-        if (hook) {
-            if (step + 1 < max_steps) continue;
-            s.ncols = std::min<int64_t>(st.hook_rank, p);   // rank-sv truncation, like `svd(Z, sv)`
-            *V_out = (double*)X;
-            *ok = true;
-            return TLSQ_OK;
-        }
         if (svp > p - 2) {  // the block may not contain every sigma >= 1/mu: full solver, or a larger block
             st.fail = SubspaceState::FAIL_SMALL;
             break;
@@ -748,7 +731,7 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
                     svp < p ? s.sigma[s.order[svp]] / inv_mu : 0.0, (int)cold);
         if (good) {
             conv = true;
-            if (cold && !hook) {
+            if (cold) {
                 // The panel changes more between the first two ALM iterations (Y is still zero in the first) than it ever does
                 // again: with the default count the first warm step misses the residual bound and a second one (~190 us on the
                 // classic path) follows.  Two more multiplications of the top columns (~13 us) avoid that; the count relaxes
@@ -759,7 +742,7 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
                 // (... and the relaxation stops at 3: probing further down costs a failed step sooner or later)
                 if (!e) st.q_floor = std::max(st.q_floor, 3);
             }
-            if (!cold && !hook) {
+            if (!cold) {
                 // a warm block that needed a second step just missed the residual bound after the first one: two more
                 // multiplications of its top columns next time are far cheaper than another step; relax again later
                 // ... and when a single step landed far below the bound (the spectral gap behind the block grows by
@@ -802,8 +785,7 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
     // ---- certificate: lambda_max(G - X_r Theta_r X_r') must be clearly below (1/mu)^2 ----
     void *Vg = nullptr, *Vs = nullptr;
     // (explicit G, at most 32 deflated columns, N < 1024: the deflation kernel reads the columns of X itself)
-    const bool no_fused_defl = dev_is(DEV_NO_FUSED_DEFLATE, '1');
-    const bool fused_deflate = !op.implicit() && svp <= 32 && N < 1024 && !no_fused_defl;
+    const bool fused_deflate = !op.implicit() && svp <= 32 && N < 1024;
     SelWeights defl_sw;
     if (svp > 0) {
         std::vector<int32_t> sel((size_t)svp);
@@ -828,9 +810,8 @@ int svd_subspace(Handle* h, const GramOp& op, int64_t N, double inv_mu, Subspace
     st.cert_margin = (1.0 - st.dlam / tau2) * (1.0 - 1e-9);
     if (!op.implicit()) {
         TLSQ_TRY(ws_get(h, WS_GD, (size_t)N * N * 8, &GD));
-        const bool no_power = dev_is(DEV_NO_POWER_CERT, '1');
         // the two dense squarings cost N^3 flops against ~16 N^2 loads for a Lanczos run: matrix powers up to N = 1024
-        st.cert_power = N <= 1024 && !no_power;
+        st.cert_power = N <= 1024;
         // Asynchronous form: the host has just read this step's results from the mailbox, so everything the certificate reads
         // (G, the block X) is complete - its two kernels go to the second stream and run beside whatever the caller queues next
         const bool async = st.cert_async && st.defer_certificate && st.cert_power && fused_deflate && svp > 0 && h->stream_b &&

@@ -883,22 +883,6 @@ __global__ __launch_bounds__(256) void k_residual_hankel(const T* __restrict__ y
     }
 }
 
-template <typename T, int VEC>
-__global__ __launch_bounds__(256) void k_div_scalar(const T* __restrict__ D, T* __restrict__ Y,
-                                                    int64_t n, T s) {
-    using V = T __attribute__((ext_vector_type(VEC)));
-    const int64_t nv = n / VEC;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int64_t i = tid; i < nv; i += stride) {
-        V d = reinterpret_cast<const V*>(D)[i];
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) d[c] = d[c] / s;  // Y ./= dual_norm   :181
-        reinterpret_cast<V*>(Y)[i] = d;
-    }
-    for (int64_t i = nv * VEC + tid; i < n; i += stride) Y[i] = D[i] / s;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void k_clamp_nonneg(T* __restrict__ A, int64_t n) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -1027,7 +1011,7 @@ int launch_shrink(Handle* h, const T* D, const T* A, const T* Y, T* E, T* Z, int
 
 // Set-up + first shrink in one pass (src/robustPCA.jl:181 and :188-192 at k = 1, where A is still zero):
 //   Y = D / s,  E = soft_th(D - 0 + (1/mu) Y, thr),  Z = D - E + (1/mu) Y
-// - the same operations in the same order as k_div_scalar followed by k_shrink (bit-identical; D - 0 is D), reading D once
+// - the same operations in the same order as Y = D / s followed by k_shrink (bit-identical; D - 0 is D), reading D once
 // instead of D twice, A and Y: 4 panel passes instead of 7.
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void k_first_shrink(const T* __restrict__ D, T* __restrict__ Y, T* __restrict__ E,
@@ -1125,7 +1109,7 @@ template <typename T>
 int launch_rebuild_update_shrink(Handle* h, const T* D, const double* Tm, const double* Vs, const T* E, T* Y, T* R,
                                  T* En, T* Zn, int64_t M, int64_t N, int64_t r, T mu, int nonnegA, T inv_mu_n, T thr_n,
                                  int nonnegE, double* sumsq, double* zero_slots, const T* hankel_y, int64_t hankel_K,
-                                 int64_t row0, int64_t row1, size_t pad_lds, HankelGeom hg) {
+                                 int64_t row0, int64_t row1, HankelGeom hg) {
     if (M <= 0 || N <= 0) return TLSQ_OK;
     if (row1 <= 0) row1 = M;   // (default: the whole panel)
     if (row0 < 0 || row0 >= row1 || row1 > M || (row0 % 2) != 0 || (row1 % 2) != 0)
@@ -1147,18 +1131,12 @@ int launch_rebuild_update_shrink(Handle* h, const T* D, const double* Tm, const 
     const dim3 grid((unsigned)(((row1 - row0) / rows + 255) / 256), (unsigned)((N + ct - 1) / ct));
 #define RUS_LAUNCH(RM, RW)                                                                                            \
     do {                                                                                                              \
-        if (pad_lds > 32768) {   /* (unused dynamic LDS: caps the resident workgroups per CU, see solver.hip) */      \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rebuild_update_shrink<T, RM, RW, true>),       \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds);                      \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rebuild_update_shrink<T, RM, RW, false>),      \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds);                      \
-        }                                                                                                             \
         if (hankel_y)                                                                                                 \
-            hipLaunchKernelGGL((k_rebuild_update_shrink<T, RM, RW, true>), grid, dim3(256), pad_lds, h->stream, hankel_y, Tm, \
+            hipLaunchKernelGGL((k_rebuild_update_shrink<T, RM, RW, true>), grid, dim3(256), 0, h->stream, hankel_y, Tm, \
                                Vs, E, Y, R, En, Zn, M, (int)N, (int)r, ct, mu, nonnegA, inv_mu_n, thr_n, nonnegE,      \
                                sumsq, zero_slots, hankel_K, row0, row1, hg);                                          \
         else                                                                                                          \
-            hipLaunchKernelGGL((k_rebuild_update_shrink<T, RM, RW, false>), grid, dim3(256), pad_lds, h->stream, D, Tm, Vs, \
+            hipLaunchKernelGGL((k_rebuild_update_shrink<T, RM, RW, false>), grid, dim3(256), 0, h->stream, D, Tm, Vs, \
                                E, Y, R, En, Zn, M, (int)N, (int)r, ct, mu, nonnegA, inv_mu_n, thr_n, nonnegE, sumsq,   \
                                zero_slots, (int64_t)0, row0, row1, hg);                                               \
     } while (0)
@@ -1353,21 +1331,6 @@ int launch_residual_hankel(Handle* h, const T* y, int64_t K, const T* A, const T
 }
 
 template <typename T>
-int launch_div_scalar(Handle* h, const T* D, T* Y, int64_t n, T s) {
-    if (n <= 0) return TLSQ_OK;
-    constexpr int VEC = 16 / sizeof(T);
-    if (aligned16(D) && aligned16(Y)) {
-        hipLaunchKernelGGL((k_div_scalar<T, VEC>), dim3(grid_for(n / VEC + 1)), dim3(256), 0,
-                           h->stream, D, Y, n, s);
-    } else {
-        hipLaunchKernelGGL((k_div_scalar<T, 1>), dim3(grid_for(n)), dim3(256), 0, h->stream, D, Y, n,
-                           s);
-    }
-    TLSQ_HIP(h, hipGetLastError());
-    return TLSQ_OK;
-}
-
-template <typename T>
 int launch_clamp_nonneg(Handle* h, T* A, int64_t n) {
     if (n <= 0) return TLSQ_OK;
     hipLaunchKernelGGL((k_clamp_nonneg<T>), dim3(grid_for(n)), dim3(256), 0, h->stream, A, n);
@@ -1461,7 +1424,7 @@ template int launch_convert<float, float>(Handle*, const float*, float*, int64_t
     template bool rebuild_update_shrink_ok<T>(const T*, const T*, T*, T*, T*, T*, int64_t, int64_t, int64_t); \
     template int launch_rebuild_update_shrink<T>(Handle*, const T*, const double*, const double*, const T*, T*, T*, \
                                                  T*, T*, int64_t, int64_t, int64_t, T, int, T, T, int, double*, double*, \
-                                                 const T*, int64_t, int64_t, int64_t, size_t, HankelGeom);            \
+                                                 const T*, int64_t, int64_t, int64_t, HankelGeom);                    \
     template int launch_zsweep<T>(Handle*, const T*, const double*, const double*, T*, const T*, T*, T*, T*, int64_t, \
                                   int64_t, int64_t, T, T, int, T, T, int, double*, double*, const T*, int64_t, int64_t, \
                                   int64_t, int, HankelGeom, T*);                                                           \
@@ -1473,7 +1436,6 @@ template int launch_convert<float, float>(Handle*, const float*, float*, int64_t
     template int launch_e_from_z<T>(Handle*, const T*, const T*, const T*, T*, int64_t, T);                           \
     template int launch_residual<T>(Handle*, const T*, const T*, const T*, T*, int64_t);          \
     template int launch_residual_hankel<T>(Handle*, const T*, int64_t, const T*, const T*, T*, int64_t, int64_t, HankelGeom); \
-    template int launch_div_scalar<T>(Handle*, const T*, T*, int64_t, T);                         \
     template int launch_clamp_nonneg<T>(Handle*, T*, int64_t);                                    \
     template int launch_maxabs<T>(Handle*, const T*, int64_t, double*);                           \
     template int launch_transpose<T>(Handle*, const T*, int64_t, int64_t, int64_t, T*, int64_t);

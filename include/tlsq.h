@@ -138,6 +138,10 @@ typedef struct tlsq_rpca_info {
      * k_zx_h + k_zty_h = one Z'(Z X)), the wide-rank sweep (sweeps.hip, k_zsweep_wide) and the fused sweep + Gram kernel
      * (fused.hip, k_fused_zgram).  The parity tests assert on them that a fixture exercised the path it was made for. */
     int64_t kern_gram_h3, kern_zx_h, kern_zty_h, kern_zsweep_wide, kern_fused_zgram;
+    /* the first shrink of the ALM loop as a kernel of its own (sweeps.hip, k_first_shrink; 0 when the fused kernel above served
+     * it), and lowrankfilter's truncation branch served from the series (hankelop.hip: the Gram matrix of H from lagged
+     * autocorrelation sums; 0 when it went through the Hankel panel) */
+    int64_t kern_first_shrink, kern_hankel_gram;
 } tlsq_rpca_info;
 
 const char* tlsq_version(void);

@@ -8,7 +8,8 @@
 #
 # NOTE: the build image has no `julia` binary, so this file is not executed by the test-suite; every call below is
 # mirrored one to one by the ctypes harness `totalleastsquares.jl_amd/engine.py`, which is.  Struct layouts are
-# checked there (tests/test_cabi_cpu.py::test_struct_sizes_match_header: sizeof(opts) = 128, sizeof(info) = 200).
+# checked there (tests/test_cabi_cpu.py::test_struct_sizes_match_header_with_the_launch_counters: sizeof(opts) = 128,
+# sizeof(info) = 272).
 #
 # Multi-GPU: ENV["TLSQ_NGPUS"] = "8" makes the one process-wide handle a tlsq_create_multi handle; rpca / lowrankfilter
 # on host arrays are then row-sharded over the GPUs inside the library (worker threads never call back into Julia; the
@@ -39,7 +40,7 @@ mutable struct RpcaOpts
     RpcaOpts() = new()
 end
 
-# mirrors `struct tlsq_rpca_info`, 256 bytes
+# mirrors `struct tlsq_rpca_info`, 272 bytes
 mutable struct RpcaInfo
     iters_done::Int64; converged::Int32; tsqr_iterations::Int32
     final_cost::Cdouble; final_mu::Cdouble; d_norm::Cdouble
@@ -51,6 +52,7 @@ mutable struct RpcaInfo
     hbm_bytes_sweeps::Cdouble; hbm_bytes::Cdouble
     sweeps_timed::Int64; hbm_bytes_sweeps_timed::Cdouble
     kern_gram_h3::Int64; kern_zx_h::Int64; kern_zty_h::Int64; kern_zsweep_wide::Int64; kern_fused_zgram::Int64
+    kern_first_shrink::Int64; kern_hankel_gram::Int64
     RpcaInfo() = new()
 end
 

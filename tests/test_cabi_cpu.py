@@ -43,11 +43,15 @@ def test_version_and_default_opts():
     assert o.memory == L.MEM_HOST and o.svd_mode == L.SVD_FULL
 
 
-def test_struct_sizes_match_header():
+def test_struct_sizes_match_header_with_the_launch_counters():
     # natural alignment, no packing: these are the sizes the Julia shim's struct mirrors must have
     assert C.sizeof(L.RpcaOpts) == 128
-    assert C.sizeof(L.RpcaInfo) == 256
+    assert C.sizeof(L.RpcaInfo) == 272
     assert C.sizeof(L.GaOpts) == 56 and C.sizeof(L.GaInfo) == 64
+    # kern_first_shrink and kern_hankel_gram are appended: the 256 bytes before them keep their layout, so a caller built
+    # against the earlier header reads every field it knows where it was
+    assert L.RpcaInfo.kern_fused_zgram.offset == 248
+    assert L.RpcaInfo.kern_first_shrink.offset == 256 and L.RpcaInfo.kern_hankel_gram.offset == 264
 
 
 def test_tls_from_vt_is_host_only_math():

@@ -196,6 +196,61 @@ def test_tall_rpca_512_columns_with_and_without_the_fused_kernel(torch_mod):
     assert np.linalg.norm(A - A0) <= 1e-6 * np.linalg.norm(A0)
 
 
+@pytest.mark.parametrize("M,N,r", [(3006, 256, 8), (4002, 512, 12)])
+def test_fused_first_shrink_runs_once(torch_mod, M, N, r):
+    """Iteration 1 on a panel the fused kernel takes (FUSED_ZGRAM_MINROWS=16: small panels qualify; M even, not a multiple of
+    2048): the fused kernel writes Y_1 and Z_1 and the Gram matrix of Z_1, and the first-shrink kernel is not launched after it
+    (kern_first_shrink == 0).  With NO_FUSED_ZGRAM=1 the first shrink runs once on its own.  Against the oracle at the bars of
+    test_gpu_parity.py; fused against split at test_tall_rpca_512_columns_with_and_without_the_fused_kernel's bar - the fused
+    kernel sums the Gram matrix in another order (2e-13 of the Gram kernel's, test_fused_sweep_gram_kernel), so the two
+    trajectories agree to rounding, not bit for bit."""
+    import tlsq_amd
+    from oracle import rpca_oracle as O
+    D = O.synth_lowrank_sparse(M, N, r, seed=M)[0]
+    out = {}
+    for tag, sw in (("fused", {}), ("split", {"NO_FUSED_ZGRAM": 1})):
+        with tlsq_amd.dev_switches(FUSED_ZGRAM_MINROWS=16, **sw):
+            e = tlsq_amd.Engine(0)
+            try:
+                out[tag] = e.rpca(D, return_report=True)
+            finally:
+                e.close()
+    (A, E, s, sv, rep), (As, Es, _, svs, reps) = out["fused"], out["split"]
+    assert rep.kern["fused_zgram"] >= 1 and rep.kern["first_shrink"] == 0, rep.kern
+    assert reps.kern["fused_zgram"] == 0 and reps.kern["first_shrink"] == 1, reps.kern
+    assert rep.iters_done == reps.iters_done and rep.svp_hist == reps.svp_hist and sv == svs
+    assert np.linalg.norm(A - As) <= 1e-10 * np.linalg.norm(As) and np.linalg.norm(E - Es) <= 1e-10 * np.linalg.norm(Es)
+    Ao, Eo, so, svo, io = O.rpca(D)
+    assert rep.iters_done == io.iters_done and rep.svp_hist == io.svp_hist and sv == svo and rep.converged == io.converged
+    assert np.allclose(rep.cost_hist, io.cost_hist, rtol=1e-6, atol=1e-12)
+    assert np.linalg.norm(A - Ao) <= 1e-8 * np.linalg.norm(Ao) and np.linalg.norm(E - Eo) <= 1e-8 * np.linalg.norm(Eo)
+
+
+def test_lazy_hankel_fused_first_shrink_runs_once(torch_mod):
+    """The same counts on lowrankfilter(y, 256), whose panel is the implicit Hankel matrix of the series: the fused kernel
+    reads y for D in iteration 1 and the first-shrink kernel does not run after it; NO_FUSED_ZGRAM=1 launches it once.  The
+    filtered series against the oracle's to 1e-8."""
+    import tlsq_amd
+    from oracle import rpca_oracle as O
+    y, noise = O.synth_series(6000, seed=13)
+    x = y + noise
+    out = {}
+    for tag, sw in (("fused", {}), ("split", {"NO_FUSED_ZGRAM": 1})):
+        with tlsq_amd.dev_switches(FUSED_ZGRAM_MINROWS=16, **sw):
+            e = tlsq_amd.Engine(0)
+            try:
+                out[tag] = e.lowrankfilter(x, 256, return_report=True)
+            finally:
+                e.close()
+    (yf, rep), (yfs, reps) = out["fused"], out["split"]
+    assert rep.kern["fused_zgram"] >= 1 and rep.kern["first_shrink"] == 0, rep.kern
+    assert reps.kern["fused_zgram"] == 0 and reps.kern["first_shrink"] == 1, reps.kern
+    assert rep.iters_done == reps.iters_done and rep.svp_hist == reps.svp_hist
+    assert np.linalg.norm(yf - yfs) <= 1e-10 * np.linalg.norm(yfs)
+    yo = O.lowrankfilter(x, 256)
+    assert np.linalg.norm(yf - yo) <= 1e-8 * np.linalg.norm(yo)
+
+
 @pytest.mark.parametrize("M,N,r,nonneg,with_r,inplace", [
     (32768, 2304, 40, 0, True, True),        # r <= 64: 32 k-steps of the 32 x 32 x 2 MFMA, zero columns behind the rank
     (32768, 2304, 64, 1, False, False),      # nonnegA / nonnegE, Z double-buffered

@@ -84,6 +84,48 @@ def test_lowrankfilter_truncation_without_the_hankel_panel(eng, Ns, n, sv, dtype
         assert np.linalg.norm(yf - yo) <= (1e-8 if dtype == np.float64 else 1e-4) * np.linalg.norm(yo)
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("Ns,n,sv", [(2000, 1000, 3), (2048, 1024, 8), (2049, 1024, 5), (400, 200, 2), (40, 20, 25), (64, 30, 40)])
+def test_lowrankfilter_truncation_on_the_widest_windows(eng, Ns, n, sv, dtype):
+    """The structured truncation branch at the widest Hankel matrices the entry accepts: L <= N/2 (src/robustPCA.jl:79) leaves
+    K = N - n + 1 >= n + 1 rows, so the window is never wider than the matrix is tall and the Gram kernel's boundary corrections
+    read only y[0 .. n - 2] and y[K .. K + n - 2] of the K + n - 1 samples.  Every case takes that branch (kern_hankel_gram == 1;
+    HANKEL_STRUCT=0 makes the panel form, 0 launches) and agrees with the panel form and the oracle at the bars of
+    test_lowrankfilter_truncation_without_the_hankel_panel.
+    sv above min(K, n) (the last two cases: sv > K > n): the library clamps the rank to min(sv, K, n) (api.hip) and so does the
+    oracle's U[:, :sv] slice - the rank-n reconstruction of H, i.e. the series itself up to rounding.  The reference's
+    U[:, 1:sv] throws a BoundsError there instead."""
+    import tlsq_amd
+    from oracle import rpca_oracle as O
+    y, noise = O.synth_series(Ns, seed=Ns + n)
+    x = (y + noise).astype(dtype)
+    yf, rep = eng.lowrankfilter(x, n, sv=sv, return_report=True)
+    with tlsq_amd.dev_switches(HANKEL_STRUCT=0):
+        yp, repp = eng.lowrankfilter(x, n, sv=sv, return_report=True)
+    assert rep.kern["hankel_gram"] == 1 and repp.kern["hankel_gram"] == 0, (rep.kern, repp.kern)
+    assert yf.dtype == dtype and yf.shape == x.shape
+    f32 = dtype == np.float32
+    assert np.linalg.norm(yf - yp) <= (2e-5 if f32 else 1e-12) * np.linalg.norm(yp)
+    yo = O.lowrankfilter(x.astype(np.float64), n, sv=sv)
+    assert np.linalg.norm(yf - yo) <= (1e-4 if f32 else 1e-8) * np.linalg.norm(yo)
+    if sv > Ns - n + 1:
+        assert np.linalg.norm(yf - x) <= (1e-5 if f32 else 1e-10) * np.linalg.norm(x)
+
+
+def test_lowrankfilter_refuses_a_window_wider_than_half_the_series(eng):
+    """n > N / 2 (K < n) is an error at the C entry as in the reference (`@assert L <= N/2`, src/robustPCA.jl:79) - for both
+    element types and whatever sv is - so no branch ever sees a Hankel matrix wider than it is tall."""
+    import ctypes as C
+    from tlsq_amd import _lib as L
+    for dt, fn in ((np.float64, eng.lib.tlsq_lowrankfilter_f64), (np.float32, eng.lib.tlsq_lowrankfilter_f32)):
+        for Ns, n, sv in ((1100, 1000, 3), (300, 200, 2), (300, 290, 20), (2047, 1024, 0)):
+            x = np.ones(Ns, dtype=dt)
+            out = np.full(Ns, 7.0, dtype=dt)
+            st = fn(eng.h, x.ctypes.data_as(C.c_void_p), Ns, 1, Ns, n, 1, sv, None, out.ctypes.data_as(C.c_void_p), Ns, None)
+            assert st == L.TLSQ_ERR_ARG, (Ns, n, sv, st)
+            assert np.all(out == 7.0)
+
+
 def test_truncation_at_config3_size_holds_no_panel(eng):
     """N = 1e7, n = 256 (BASELINE config 3's series) with sv = 4: the two 20 GB panels of the materialised form are never
     allocated - a fresh handle ends up with the series, the 1e7 x 4 factor and small matrices - and the filter does what the

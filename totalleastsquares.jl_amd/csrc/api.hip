@@ -156,6 +156,7 @@ static int lowrankfilter_impl(tlsq_handle h, const T* y, int64_t Nx, int64_t Dch
         info->svp_hist = sh;
         info->hist_capacity = cap;
     }
+    h->kern_hankel_gram = 0;
     const double t0 = now_ms();
     const bool dev = opts && opts->memory == TLSQ_MEM_DEVICE;
     const int64_t Kg = (Nx - n) / lag + 1, LD = n * Dch;   // rows of the whole Hankel matrix
@@ -261,7 +262,10 @@ static int lowrankfilter_impl(tlsq_handle h, const T* y, int64_t Nx, int64_t Dch
         TLSQ_TRY(launch_gather_scale_arg(h, V, n, sw, r_sv, nullptr, (double*)Vs));
         TLSQ_TRY(hankel_times<T>(h, yw, K, Kp, n, (const double*)Vs, n, r_sv, (double*)Tm, Kp));
         TLSQ_TRY(launch_unhankel_factors<T>(h, (const double*)Tm, Kp, (const double*)Vs, n, r_sv, K, n, Nx, (T*)dy));
-        if (info) info->jacobi_sweeps = sweeps;
+        if (info) {
+            info->jacobi_sweeps = sweeps;
+            info->kern_hankel_gram = h->kern_hankel_gram;
+        }
     } else {                                                                                  // :123-126
         SmallSvd s;
         double* V = nullptr;

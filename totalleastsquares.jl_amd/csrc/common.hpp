@@ -22,6 +22,13 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// Layout of Handle::pinned (kPinnedBytes of pinned host memory).  Synchronous read-backs copy to its front and must fit in
+// [0, kPinnedReadbackBytes).  The last 64 bytes belong to the asynchronous max |D| of launch_maxabs_begin alone: its copy is
+// still pending on the second stream while the set-up's Lanczos read-backs land at the front.
+constexpr size_t kPinnedBytes = (size_t)1 << 16;
+constexpr size_t kPinnedMaxabsOff = kPinnedBytes - 64;
+constexpr size_t kPinnedReadbackBytes = kPinnedMaxabsOff;
+
 struct Comm;  // RCCL state (runtime.hip)
 struct Stager;   // pinned staging pipeline of host-pointer calls (staging.hip)
 
@@ -34,7 +41,7 @@ struct Handle {
     std::string err;
     // grow-only device workspace, keyed by slot
     std::vector<DevBuf> ws;
-    // pinned host scratch for small readbacks
+    // pinned host scratch for small readbacks (kPinnedBytes; layout: kPinnedReadbackBytes, kPinnedMaxabsOff)
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
     // pinned staging ring for small host->device uploads (index lists, scale factors): the copy is asynchronous
@@ -79,6 +86,8 @@ struct Handle {
     // launches of the shape-dependent kernels since the last rpca_core entry (tlsq_rpca_info::kern_*)
     bool fused_warm_done = false;   // fused_zgram_warm has run on this handle's device
     int64_t kern_gram_h3 = 0, kern_zx_h = 0, kern_zty_h = 0, kern_zsweep_wide = 0, kern_fused_zgram = 0;
+    int64_t kern_first_shrink = 0;
+    int64_t kern_hankel_gram = 0;   // (since the last lowrankfilter entry)
 };
 
 }  // namespace tlsq

@@ -28,7 +28,8 @@ __global__ __launch_bounds__(1024) void k_hankel_autocorr(const T* __restrict__ 
     extern __shared__ __attribute__((aligned(16))) double sw[];   // HG_CHUNK + n samples
     const int64_t t0 = (int64_t)blockIdx.x * HG_CHUNK;
     const int64_t len = (K - t0 < HG_CHUNK) ? K - t0 : HG_CHUNK;   // samples t of this chunk
-    for (int64_t e = threadIdx.x; e < len + n - 1; e += blockDim.x) sw[e] = (double)y[t0 + e];   // (t + d <= K + n - 2: the last sample)
+    // (t0 + len <= K, so t0 + e <= K + n - 2: the last sample, also when K < n; thread d reads up to sw[len - 1 + d], d < n)
+    for (int64_t e = threadIdx.x; e < len + n - 1; e += blockDim.x) sw[e] = (double)y[t0 + e];
     __syncthreads();
     const int d = threadIdx.x;
     if (d >= n) return;
@@ -48,8 +49,10 @@ __global__ __launch_bounds__(1024) void k_hankel_autocorr(const T* __restrict__ 
 template <typename T>
 __global__ __launch_bounds__(1024) void k_hankel_gram_fill(const T* __restrict__ y, int64_t K, int n, const double* __restrict__ part,
                                                            int nblk, double* __restrict__ G) {
-    __shared__ double sa[2048], sb[2048];   // y[0 .. 2 n - 2], y[K .. K + n - 2] (n <= 1024): what the corrections read
-    for (int e = threadIdx.x; e < 2 * n - 1; e += blockDim.x) sa[e] = (double)y[e];
+    // y[0 .. n - 2] and y[K .. K + n - 2] (n <= 1024): what the corrections read.  Both lie inside the K + n - 1 samples whatever
+    // K is; a wide window (K < n) has fewer than 2 n - 1 samples, so nothing beyond y[n - 2] is loaded into sa.
+    __shared__ double sa[1024], sb[1024];
+    for (int e = threadIdx.x; e < n - 1; e += blockDim.x) sa[e] = (double)y[e];
     for (int e = threadIdx.x; e < n - 1; e += blockDim.x) sb[e] = (double)y[K + e];
     __syncthreads();
     const int d = threadIdx.x;
@@ -109,6 +112,7 @@ template <typename T>
 int hankel_gram(Handle* h, const T* y, int64_t K, int64_t n, double* G) {
     if (!hankel_structured_ok(K, n, 1)) return set_err(h, TLSQ_ERR_ARG, "hankel_gram: n = %lld", (long long)n);
     const int64_t nblk = (K + HG_CHUNK - 1) / HG_CHUNK;
+    ++h->kern_hankel_gram;
     void* part;
     TLSQ_TRY(ws_get(h, WS_SLAB, (size_t)nblk * n * 8, &part));
     const int threads = (int)std::max<int64_t>(256, (n + 63) / 64 * 64);

@@ -552,7 +552,7 @@ int lanczos_begin(Handle* h, LanczosRun& r, const double* G, int64_t N, int64_t 
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds_multi));
     }
     r.lds = (size_t)(N + 8) * 8;
-    if (r.lds > 150 * 1024 || (size_t)(2 * r.cap) * 8 + 64 > h->pinned_bytes) {
+    if (r.lds > 150 * 1024 || (size_t)(2 * r.cap) * 8 + 64 > kPinnedReadbackBytes) {
         r.unsupported = true;
         return TLSQ_OK;
     }
@@ -879,7 +879,7 @@ int lanczos_lmax_op(Handle* h, int64_t N, const LzApply& apply, double rel_tol, 
     if (max_steps > (int)N) max_steps = (int)N;
     if (max_steps < 1) max_steps = 1;
     const int cap = max_steps + 2;
-    if ((size_t)(2 * cap) * 8 + 64 > h->pinned_bytes) return 1;
+    if ((size_t)(2 * cap) * 8 + 64 > kPinnedReadbackBytes) return 1;
     void* stv;
     TLSQ_TRY(ws_get(h, WS_LZOP, (8 + 3 * (size_t)N + 2 * (size_t)cap + 16) * 8, &stv));
     double* st = (double*)stv;

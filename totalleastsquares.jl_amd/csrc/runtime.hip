@@ -557,7 +557,7 @@ int tlsq_create(int device_id, tlsq_handle* out) {
             delete h;
             return TLSQ_ERR_HIP;
         }
-    h->pinned_bytes = 1 << 16;
+    h->pinned_bytes = kPinnedBytes;
     if (hipHostMalloc(&h->pinned, h->pinned_bytes, hipHostMallocDefault) != hipSuccess) {
         delete h;
         return TLSQ_ERR_OOM;

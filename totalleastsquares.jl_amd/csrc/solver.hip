@@ -548,7 +548,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
     };
     h->out_factors = false;
     h->absmax_panel = nullptr;   // (no panel of this call has been written yet)
-    h->kern_gram_h3 = h->kern_zx_h = h->kern_zty_h = h->kern_zsweep_wide = h->kern_fused_zgram = 0;
+    h->kern_gram_h3 = h->kern_zx_h = h->kern_zty_h = h->kern_zsweep_wide = h->kern_fused_zgram = h->kern_first_shrink = 0;
     if (!(zmode && ro.factors_out)) TLSQ_TRY(need_A());
     // classic loop: E and Z are double-buffered: the fused update(k)+shrink(k+1) sweep writes E_{k+1}, Z_{k+1} while E_k, Z_k
     // must survive in case iteration k is the last one
@@ -1286,10 +1286,11 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
                         first_fused = true;
                     }
                 }
-                if (!first_fused)
+                if (!first_fused) {
                     host_mark("first shrink");
                     TLSQ_TRY(launch_first_shrink<T>(h, D, Y, zmode ? (T*)nullptr : E, Z, n, (T)dual_norm, (T)inv_mu, (T)thr,
                                                     ro.nonnegE ? 1 : 0));
+                }
                 y_pending = false;
                 hbm_sweeps += (zmode ? 3.0 : 4.0) * panel_bytes - (first_fused && ro.hankel_y ? panel_bytes : 0.0);
             } else {
@@ -2274,6 +2275,7 @@ int rpca_core(Handle* h, const T* D, int64_t M, int64_t N, const ResolvedOpts& r
         info->kern_zty_h = h->kern_zty_h;
         info->kern_zsweep_wide = h->kern_zsweep_wide;
         info->kern_fused_zgram = h->kern_fused_zgram;
+        info->kern_first_shrink = h->kern_first_shrink;
     }
     if (sv_out) *sv_out = sv;
 

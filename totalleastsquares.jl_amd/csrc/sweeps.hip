@@ -1050,6 +1050,7 @@ __global__ __launch_bounds__(256) void k_first_shrink(const T* __restrict__ D, T
 template <typename T>
 int launch_first_shrink(Handle* h, const T* D, T* Y, T* E, T* Z, int64_t n, T s, T inv_mu, T thr, int nonnegE) {
     if (n <= 0) return TLSQ_OK;
+    ++h->kern_first_shrink;
     constexpr int VEC = 16 / sizeof(T);
     if (aligned16(D) && aligned16(Y) && aligned16(E) && aligned16(Z))
         hipLaunchKernelGGL((k_first_shrink<T, VEC>), dim3(grid_for(n / VEC + 1)), dim3(256), 0, h->stream, D, Y, E, Z, n, s,
@@ -1357,6 +1358,9 @@ int launch_maxabs(Handle* h, const T* x, int64_t n, double* host_out) {
 // The same in two halves: the pass is queued on the handle's SECOND stream (it is memory-bound and overlaps the Gram matrix of the
 // set-up, which is not) and its result is read when the caller needs it - no host round trip between the two kernels of the
 // set-up.  x must not be written by anything queued on the main stream in between.
+// Rule: the result's copy lands at h->pinned + kPinnedMaxabsOff, a word no other read-back writes.  Between begin and end the
+// main stream keeps copying to the front of h->pinned (the set-up's Lanczos read-backs without the mailbox: 64 + 16 (N + 2)
+// bytes, in stream order after this copy), and every such read-back is bounded by kPinnedReadbackBytes.
 int second_stream(Handle* h);   // (runtime.hip)
 template <typename T>
 int launch_maxabs_begin(Handle* h, const T* x, int64_t n) {
@@ -1372,12 +1376,12 @@ int launch_maxabs_begin(Handle* h, const T* x, int64_t n) {
         hipLaunchKernelGGL((k_maxabs<T>), dim3(grid_for(n)), dim3(256), 0, h->stream_b, x, n, d);
         TLSQ_HIP(h, hipGetLastError());
     }
-    TLSQ_HIP(h, hipMemcpyAsync(reinterpret_cast<char*>(h->pinned) + 2048, d, 8, hipMemcpyDeviceToHost, h->stream_b));
+    TLSQ_HIP(h, hipMemcpyAsync(reinterpret_cast<char*>(h->pinned) + kPinnedMaxabsOff, d, 8, hipMemcpyDeviceToHost, h->stream_b));
     return TLSQ_OK;
 }
 int launch_maxabs_end(Handle* h, double* host_out) {
     TLSQ_HIP(h, hipStreamSynchronize(h->stream_b));
-    memcpy(host_out, reinterpret_cast<char*>(h->pinned) + 2048, 8);
+    memcpy(host_out, reinterpret_cast<char*>(h->pinned) + kPinnedMaxabsOff, 8);
     return TLSQ_OK;
 }
 template int launch_maxabs_begin<double>(Handle*, const double*, int64_t);
